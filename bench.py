@@ -19,6 +19,11 @@ every rank composites its four cameras over the whole 4 M-Gaussian scene. Per-GP
 renders 4N images per step: weak scaling, ideal throughput = N x the "c4_single_gpu" value of the N=1 line.
 `--workload c3shard` keeps the older shape (the 1 M c3 scene sharded, one camera per rank).
 
+A plain run sets up, warms up, times the K steps and prints the headline fields (metric, value, unit, ms_per_step, ...).
+Everything else below - the repeated and instrumented windows, the GPU state under load, the stage table, the other row
+layout, the roofline, the c5 / c4_single_gpu / c2 / train-step sub-records and the CPU baseline - runs with `--full` only.
+`--dump-outputs DIR` writes what the last timed step computed (rendered images, parameter gradients) as DIR/<name>.npy.
+
 metric = Mpixels/s fwd+bwd = (images * H * W * steps) / wall time, whole job.
 roofline  = dominant kernel (the compositing backward) priced against HBM: algorithmic bytes per launch
             (SURVEY.md §8(d)) / its mean launch duration measured live with HIP events on the launch stream;
@@ -44,6 +49,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s mea
 FP32_PEAK_TFLOPS = 157.3
 N_SIMDS = 256 * 4  # 256 CUs x 4 SIMDs
 NAMES = ("means", "quats", "scales", "opacities", "colors")
+# --dump-outputs: images of more pixels and gradients of more Gaussians than these are written as a seeded sample of rows
+# (at most 2^21 x 4 + 2^16 x 59 float32 = 47.5 MB in all, under the 64 MB a dump may take)
+DUMP_PIXELS, DUMP_GAUSSIANS = 1 << 21, 1 << 16
+DUMP_MAX_BYTES = 64 << 20
 
 
 def make_workload(n_gaussians: int, device, n_cameras: int = 1, seed: int = 0, rank: int = 0, world: int = 1):
@@ -195,6 +204,38 @@ def smi_state_under_load(step_fn, device_index: int, sample: bool, fixed_steps: 
     return keep or None
 
 
+def sample_rows(x, max_rows: int, seed: int):
+    """`x` itself when it has at most `max_rows` rows (first axis), else a fixed seeded choice of rows in ascending order."""
+    if x.shape[0] <= max_rows:
+        return x
+    idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(seed))[:max_rows].sort().values
+    return x[idx.to(x.device)]
+
+
+def step_outputs(render_colors, render_alphas, leaves):
+    """What a caller of the timed path receives from one step, as float32 host arrays: the rendered images and the gradients
+    of the Gaussian parameters. Images of more than DUMP_PIXELS pixels become a sample of pixel rows ([n, channels]),
+    gradients of more than DUMP_GAUSSIANS Gaussians a sample of Gaussian rows; the same rows on every run."""
+    out = {}
+    for name, x in (("render_colors", render_colors), ("render_alphas", render_alphas)):
+        if x.shape[:-1].numel() > DUMP_PIXELS:
+            x = sample_rows(x.reshape(-1, x.shape[-1]), DUMP_PIXELS, seed=1)
+        out[name] = x
+    for k, t in leaves.items():
+        out["grad_" + k] = sample_rows(t.grad, DUMP_GAUSSIANS, seed=2)
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def save_outputs(out_dir: str, arrays: dict) -> None:
+    import numpy as np
+
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def pair_stats(meta, n_images, W, H):
     """Work counters of the compositing pass (C-ABI gsx_raster3d_pair_stats: instrumentation, replays the forward walk)."""
     from gsplat_amd._cabi import call, ptr
@@ -229,8 +270,17 @@ def main():
                     help="extra repeats of the K-step timed window after the headline one (reported as windows_ms, value_median, "
                          "value_best); 0 switches them off")
     ap.add_argument("--lean", action="store_true",
-                    help="only warmup + timed steps (no stage table, no sub-records, no CPU baseline): for rocprofv3 runs")
+                    help="the headline window with HIP events around the compositing launches, and the roofline from them (no "
+                         "repeats, stage table, sub-records or CPU baseline): for rocprofv3 runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window, everything else: its repeats, the GPU state, the stage table, the other "
+                         "row layout, the roofline, the sub-records and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rendered images, gradients of the Gaussian parameters; "
+                         "large ones as a fixed sample of rows) as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: launch the N ranks ourselves, one per GPU, the way gsplat/distributed.py:319-375
@@ -307,7 +357,7 @@ def main():
     # rows need no id columns in the all-to-all (48 B/row instead of 64 B/visible row) and no compaction pass
     packed = bool(args.packed)
 
-    def make_step(leaves, sc, packed=packed, distributed=distributed):
+    def make_step(leaves, sc, packed=packed, distributed=distributed, keep=None):
         def step():
             for t in leaves.values():
                 t.grad = None
@@ -315,10 +365,13 @@ def main():
                 leaves["means"], leaves["quats"], leaves["scales"], leaves["opacities"], leaves["colors"], sc["viewmats"],
                 sc["Ks"], W, H, sh_degree=3, packed=packed, tile_size=TILE, distributed=distributed)
             rc.sum().backward()
+            if keep is not None:
+                keep["render_colors"], keep["render_alphas"] = rc.detach(), ra.detach()
             return meta
         return step
 
-    step = make_step(leaves, sc)
+    last = {} if args.dump_outputs else None  # the images of the last step, for --dump-outputs only
+    step = make_step(leaves, sc, keep=last)
 
     def barrier():
         if distributed:
@@ -361,6 +414,43 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    windows_s = [max_over_ranks(elapsed)]
+    elapsed = windows_s[0]  # max over ranks of the headline window
+    # taken before any later step of --full replaces the gradients
+    outputs = step_outputs(last["render_colors"], last["render_alphas"], leaves) if last is not None and rank == 0 else None
+    images = n_cams * n_gpus
+    pixels = images * W * H
+    mpix_s = pixels * args.steps / elapsed / 1e6
+    if workload == "c3" and not distributed:
+        wl = "c3: 1M synthetic Gaussians, 1x1920x1080, SH deg 3, 16x16 tiles, fwd+bwd"
+    else:
+        wl = (f"{workload}: {n_total} synthetic Gaussians stride-sharded over {n_gpus} rank(s) ({n_local} per rank), "
+              f"{n_cams}x1920x1080 camera(s) per rank ({n_cams * n_gpus} images per step), SH deg 3, 16x16 tiles, fwd+bwd"
+              + (", distributed=True (all-gather cameras + all-to-all projected rows)" if distributed else ""))
+    result = {
+        "metric": "Mpixels/s fwd+bwd @1M Gaussians/1080p" if workload != "c4" else
+                  "Mpixels/s fwd+bwd @4M Gaussians sharded / 4x1080p cameras per GPU",
+        "value": round(mpix_s, 2), "unit": "Mpixels/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": wl, "gaussians_per_gpu": n_local, "cameras_per_gpu": n_cams, "packed": packed,
+                   "parallelism": f"gaussian-sharded x{n_gpus}" if distributed else "single"},
+        **({"rehearsal": True, "rehearsal_note": "all ranks on ONE GPU over gloo: code-path check, timings meaningless"}
+           if rehearsal else {}),
+    }
+
+    def finish():
+        if outputs is not None:
+            save_outputs(args.dump_outputs, outputs)
+        if rank == 0:
+            print(json.dumps(result), file=json_out, flush=True)
+        if distributed:
+            dist.destroy_process_group()
+
+    if not (args.full or args.lean):
+        finish()
+        return
+
     # The headline stays the window the driver specified (the K steps above). The SAME window is then repeated: a 20-step
     # window is ~20 ms, a 3 % kernel change is invisible in one of them next to box-to-box spread - the repeats give run noise
     # (min / median / max) on THIS box, the SMI state below says which box it was.
@@ -368,7 +458,6 @@ def main():
     exchange_bytes = None
     if distributed:
         from gsplat_amd import distributed as _gd
-    windows_s = [max_over_ranks(elapsed)]
     if args.lean:  # profiling runs: one window only, instrumented
         instrumented_window_s = windows_s[0]
     else:
@@ -429,11 +518,6 @@ def main():
                     if pk:
                         low["visible_fraction"] = round(m_l["gaussian_ids"].numel() / float(n_local * n_cams), 4)
                 other[key] = dict(low, workload=f"c3 scene, far_plane = {far:g} (ms per step, both layouts)")
-    elapsed = windows_s[0]  # max over ranks of the headline window
-
-    images = n_cams * n_gpus
-    pixels = images * W * H
-    mpix_s = pixels * args.steps / elapsed / 1e6
 
     # ---- roofline of the dominant kernel (rank 0's launches) -------------------------------------
     M = int(meta["isect_ids"].numel())
@@ -577,23 +661,8 @@ def main():
             gbs = nbytes / (per_step_ms[k] * 1e-3) / 1e9
             stage_roofline[k.replace("gsx_", "")] = {"achieved_GBps": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)}
 
-    if workload == "c3" and not distributed:
-        wl = "c3: 1M synthetic Gaussians, 1x1920x1080, SH deg 3, 16x16 tiles, fwd+bwd"
-    else:
-        wl = (f"{workload}: {n_total} synthetic Gaussians stride-sharded over {n_gpus} rank(s) ({n_local} per rank), "
-              f"{n_cams}x1920x1080 camera(s) per rank ({n_cams * n_gpus} images per step), SH deg 3, 16x16 tiles, fwd+bwd"
-              + (", distributed=True (all-gather cameras + all-to-all projected rows)" if distributed else ""))
-    result = {
-        "metric": "Mpixels/s fwd+bwd @1M Gaussians/1080p" if workload != "c4" else
-                  "Mpixels/s fwd+bwd @4M Gaussians sharded / 4x1080p cameras per GPU",
-        "value": round(mpix_s, 2), "unit": "Mpixels/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": wl, "gaussians_per_gpu": n_local, "cameras_per_gpu": n_cams, "packed": packed,
-                   "parallelism": f"gaussian-sharded x{n_gpus}" if distributed else "single"},
+    result.update({
         "roofline": roofline,
-        **({"rehearsal": True, "rehearsal_note": "all ranks on ONE GPU over gloo: code-path check, timings meaningless"}
-           if rehearsal else {}),
         # the driver-specified window first, then its repeats: ms per step of each, and the throughput of the median / best window
         "windows_ms": [round(w / args.steps * 1e3, 4) for w in windows_s],
         "instrumented_window_ms": round(instrumented_window_s / args.steps * 1e3, 4),  # HIP events around the compositing launches
@@ -604,7 +673,7 @@ def main():
                              "bwd": round(t_bwd, 4) if t_bwd == t_bwd else None},  # HIP events inside the timed region
         "stage_ms_per_step": {k.replace("gsx_", ""): round(v, 4) for k, v in sorted(per_step_ms.items())},
         "stage_roofline_hbm": stage_roofline,
-    }
+    })
     if other is not None:
         result["other_layout"] = other
     if exchange_bytes is not None:
@@ -803,10 +872,7 @@ def main():
                 "config": c1["config"], "reference_mpixels_per_s": c1["reference_cpu"]["mpixels_per_s"],
                 "reference_s_per_step": c1["reference_cpu"]["s_per_step"], "port_mpixels_per_s": c1["port_cpu"]["mpixels_per_s"],
                 "cores": c1["host"].get("torch_threads"), "host": c1["host"], "kind": "reference", "source": c1["source"]}
-    if rank == 0:
-        print(json.dumps(result), file=json_out, flush=True)
-    if distributed:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -2,9 +2,9 @@
 schemas verbatim against the reference's ext.cpp, the argument mapping of gsplat::rasterization_3dgs / _2dgs onto the
 orchestrator, and the reference's own gsplat.rasterization() Python driving them through the shim. No kernels run here
 (the orchestrator is stubbed); the numerics of the composite ops are covered by tests/test_gpu_composite.py."""
+import json
 import os
 import pickle
-import re
 import subprocess
 import sys
 
@@ -56,20 +56,14 @@ def test_custom_classes(ops):
 
 
 def _reference_schemas():
-    src = open(os.path.join(REF, "gsplat", "cuda", "ext.cpp")).read()
-    out = {}
-    for m in re.finditer(r"m\.def\(\s*((?:\"[^\"]*\"\s*)+)\)", src):
-        text = "".join(re.findall(r"\"([^\"]*)\"", m.group(1)))
-        name = text.split("(", 1)[0].strip()
-        out[name] = text
-    return out
+    """The reference's operator schemas, pinned by oracle/pin_schemas_against_reference.py."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_schemas.json")) as f:
+        return json.load(f)
 
 
 def test_schemas_are_the_references(ops):
     """Every operator this backend defines has, character for character after parsing, the schema the reference's
     TORCH_LIBRARY(gsplat) block declares (ext.cpp:983-1258)."""
-    if not os.path.isdir(os.path.join(REF, "gsplat")):
-        pytest.skip("reference checkout not present")
     ref = _reference_schemas()
     ours = dict(ops.SCHEMAS, **ops.COMPOSITE_SCHEMAS, **ops.CLASS_SCHEMAS)
     assert {"rasterization_3dgs", "rasterization_2dgs", "assemble_proj_features_unpacked_fwd"} <= set(ours)

@@ -106,7 +106,7 @@ def test_bench_two_rank_path_rehearsal():
     env = dict(os.environ, GSPLAT_BENCH_REHEARSAL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--gaussians", "60000"]
+           "--gaussians", "60000", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -136,7 +136,7 @@ def test_bench_eight_rank_path_rehearsal():
     env["GSPLAT_BENCH_REHEARSAL"] = "1"
     n_local = 5000
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--gaussians", str(n_local),
-           "--no-extra", "--windows", "1"]
+           "--no-extra", "--windows", "1", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -181,7 +181,7 @@ def test_bench_single_gpu_line_has_the_contract_fields():
         pytest.skip("needs a ROCm GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--gaussians", "100000", "--no-extra",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -205,3 +205,48 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     assert r["value_best"] >= r["value_median"] > 0 and r["instrumented_window_ms"] > 0
     for view in ("fwd", "bwd", "fwd_plus_bwd"):
         assert 0 < roof[view]["frac"] < 1 and roof[view]["launch_ms"] > 0, view
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain N = 1 run times the headline window only (no roofline, repeats or sub-records) and `--dump-outputs` writes what
+    its last timed step computed: the image, as rendered again here from the same seeded workload, and sampled gradients."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    if not torch.cuda.is_available():
+        pytest.skip("needs a ROCm GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    n = 100000
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--gaussians", str(n),
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "Mpixels/s" and r["higher_is_better"] is True
+    assert r["dtype"] == "f32" and r["ms_per_step"] > 0
+    assert r["value"] == pytest.approx(1920 * 1080 / (r["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    for key in ("roofline", "windows_ms", "other_layout", "c5", "c4_single_gpu", "cpu_baseline", "stage_ms_per_step"):
+        assert key not in r, key
+    files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(files) == {"render_colors", "render_alphas", "grad_means", "grad_quats", "grad_scales", "grad_opacities",
+                          "grad_colors"}
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["render_colors"].shape == (1, 1080, 1920, 3) and files["render_alphas"].shape == (1, 1080, 1920, 1)
+    assert files["grad_means"].shape == (1 << 16, 3) and files["grad_colors"].shape == (1 << 16, 16, 3)
+    assert np.isfinite(files["grad_colors"]).all() and np.abs(files["grad_colors"]).sum() > 0
+
+    sys.path.insert(0, ROOT)
+    import bench
+    import gsplat_amd
+
+    sc, W, H = bench.make_workload(n, "cuda")
+    leaves = {k: sc[k].clone().requires_grad_(True) for k in NAMES}
+    rc, ra, _ = gsplat_amd.rasterization(*(leaves[k] for k in NAMES), sc["viewmats"], sc["Ks"], W, H, sh_degree=3, packed=False,
+                                         tile_size=bench.TILE)
+    np.testing.assert_allclose(files["render_colors"], rc.detach().cpu().numpy(), rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(files["render_alphas"], ra.detach().cpu().numpy(), rtol=1e-4, atol=1e-5)
