@@ -478,21 +478,18 @@ __global__ void __launch_bounds__(256) raster2d_bwd_kernel(const Raster2DArgs a)
     }
 }
 
-// ---- backward, ONE WAVE PER TILE (the decomposition of variant W in raster3d_bwd.hip) -------------------------------------
+// ---- backward, ONE WAVE PER HALF TILE (the decomposition of variant W in raster3d_bwd.hip) --------------------------------
 // The kernel above reduces K = 15 + D values per (wave, surfel) pair over the 64 pixels of one 8 x 8 quadrant - 62 of its
 // ~160 VALU instructions per pair, 2.8 pairs per staged surfel on c5 - and combines the four waves of a tile with LDS float
-// atomics between workgroup barriers. Here a tile is one wave64 and a lane owns the same pixel of each quadrant: the K values
-// are first summed over the lane's (up to) four pixels with plain adds and reduced ONCE per (tile, surfel); the totals pass
+// atomics between workgroup barriers. Here half a tile is one wave64 and a lane owns the same pixel of each of its quadrants: the
+// K values are first summed over the lane's pixels with plain adds and reduced ONCE per (half tile, surfel); the totals pass
 // through a 2-slot LDS scratch, and lane c of slot g turns them into column c of the gradient row (the cross products of the
 // ray-transform gradient are linear in nine moments, as above) and adds it to HBM. Wave-private staging (64 surfels per
 // batch, one per lane, rows requested one batch ahead), a 4-bit quadrant mask per staged surfel from the two-stage cull,
 // no __syncthreads, no LDS atomics, no accumulator table; tiles longest-first (tile_order.hip). D <= 4, 16 x 16 tiles, no
-// absgrad. Parity-green (tests/test_gpu_variants.py) and selectable (GSX_RASTER2D_BWD=w); not the default, see launch2_bwd.
-#ifndef GSX_BWD2_H_WAVES // the half-tile variant (NQ = 2)
+// absgrad. The default for those (see launch2_bwd).
+#ifndef GSX_BWD2_H_WAVES
 #define GSX_BWD2_H_WAVES 4
-#endif
-#ifndef GSX_BWD2_W_WAVES // 168 VGPRs (three waves per SIMD) spill 51 registers at four channels: two
-#define GSX_BWD2_W_WAVES 2
 #endif
 #ifndef GSX_BWD2_W_STAGE_AHEAD
 #define GSX_BWD2_W_STAGE_AHEAD 1
@@ -508,13 +505,15 @@ struct Bwd2WCfg {
     static constexpr size_t smem = (size_t)BATCH * (8 * sizeof(float4)) + sizeof(float) * SLOTS * TP;
 };
 
-// NQ = 4: one wave per tile (four pixels per lane). NQ = 2 (round 5): one wave per HALF tile - the quadrants above or below
-// the tile's middle, two pixels per lane: half the per-pixel state (three waves per SIMD instead of two), one reduction per
-// (half tile, surfel) instead of one per (quadrant, surfel) as in the four-wave kernel; the halves of a tile are workgroups b
-// and b + 8 (the same XCD, dispatched next to each other: the staged surfels are still in its L2).
+// One wave per HALF tile: the quadrants above or below the tile's middle, two pixels per lane (NQ = 2 quadrants per wave) -
+// half the per-pixel state of one wave per whole tile (NQ = 4: two waves per SIMD, 1.83 ms on c5 like the reduction kernel;
+// profiles/r09_ab.md #42), one reduction per (half tile, surfel) instead of one per (quadrant, surfel) as in the four-wave
+// kernel; the halves of a tile are workgroups b and b + 8 (the same XCD, dispatched next to each other: the staged surfels are
+// still in its L2). NQ stays a template parameter so that the kernel keeps the name its profiles record.
 template <int CH, bool DIST, int NQ>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NQ == 2 ? GSX_BWD2_H_WAVES : (DIST ? 2 : GSX_BWD2_W_WAVES)))) raster2d_bwd_w_kernel(const Raster2DArgs a)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSX_BWD2_H_WAVES))) raster2d_bwd_w_kernel(const Raster2DArgs a)
 {
+    static_assert(NQ == 2, "one wave per half tile");
     using Cfg           = Bwd2WCfg<CH>;
     constexpr int K     = Cfg::K;
     constexpr int KQ    = Cfg::KQ;
@@ -827,24 +826,12 @@ static int launch2_bwd(const Raster2DArgs &a, hipStream_t stream)
     const uint32_t grid  = ((n_blocks + 7u) / 8u) * 8u;
     const uint32_t block = a.tile_size <= 8 ? 64u : 256u;
     if constexpr (!ABS && CH <= 4) {
-        if (raster2d_bwd_m_applies(a, ABS)) return raster2d_bwd_m_launch(a, stream); // the sums as one matrix product
-        // w: one wave per tile: on c5 it issues 19 % fewer VALU and half the LDS instructions than the reduction kernel but
-        // needs 246 VGPRs - two waves per SIMD, 75 % VALU issue where the reduction kernel (five waves) runs at 97 % - and
-        // takes the same time (profiles/r08_ab.md #19, #20). h keeps half of that saving at 152 VGPRs, three waves per SIMD
-        // GSX_RASTER2D_BWD = h (default since round 5: one wave per HALF tile, 1.75 ms on c5) | r (the four-wave reduction
-        // kernel below, 1.83) | w (one wave per tile, 1.83) | m (raster2d_bwd_m.hip, 2.74); read once per process
+        // GSX_RASTER2D_BWD = h (default: one wave per half tile, 1.75 ms on c5) | r (the four-wave reduction kernel below, 1.83
+        // ms; profiles/r09_ab.md #42); read once per process
         static const char use = [] {
             const char *e = getenv("GSX_RASTER2D_BWD");
-            if (e && (e[0] == 'w' || e[0] == 'W')) return 'w';
-            if (e && (e[0] == 'r' || e[0] == 'R')) return 'r';
-            if (e && (e[0] == 'm' || e[0] == 'M')) return 'm';
-            return 'h';
+            return (e && (e[0] == 'r' || e[0] == 'R')) ? 'r' : 'h';
         }();
-        if (a.tile_size == 16 && use == 'w') {
-            if (a.v_render_distort) raster2d_bwd_w_kernel<CH, true, 4><<<dim3(grid), dim3(64), Bwd2WCfg<CH>::smem, stream>>>(a);
-            else raster2d_bwd_w_kernel<CH, false, 4><<<dim3(grid), dim3(64), Bwd2WCfg<CH>::smem, stream>>>(a);
-            return check_launch("raster2d_bwd_w");
-        }
         if (a.tile_size == 16 && use == 'h') { // one wave per half tile
             if (a.v_render_distort) raster2d_bwd_w_kernel<CH, true, 2><<<dim3(2u * grid), dim3(64), Bwd2WCfg<CH>::smem, stream>>>(a);
             else raster2d_bwd_w_kernel<CH, false, 2><<<dim3(2u * grid), dim3(64), Bwd2WCfg<CH>::smem, stream>>>(a);

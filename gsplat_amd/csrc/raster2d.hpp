@@ -1,5 +1,5 @@
 // Shared pieces of the 2DGS (surfel) compositing kernels: argument block, per-sample evaluation, wave-level culling.
-// Used by raster2d.hip (forward, reduction / one-wave backward) and raster2d_bwd_m.hip (backward on the matrix cores).
+// Used by raster2d.hip (forward, reduction / one-wave backward).
 // Semantics restated from gsplat/cuda/csrc/RasterizeToPixels2DGSSerialBatchFwd.cu:43-465 and
 // RasterizeToPixels2DGSSerialBatchBwd.cu:41-700 (see raster2d.hip).
 #pragma once
@@ -141,12 +141,5 @@ __device__ __forceinline__ bool surfel_reaches_rect(const float4 A /*zeta_c, mea
     const float mag = fmaf(X, fmaf(a, X, fmaf(fabsf(b), Y, fabsf(d))), fmaf(Y, fmaf(c, Y, fabsf(e)), fabsf(f)));
     return !(fminf(F(xe, ys), F(xs, ye)) > 1e-4f * mag); // NaN: keep
 }
-
-// Matrix-core backward (raster2d_bwd_m.hip): <= 4 channels, 16 x 16 tiles, no absgrad. GSX_RASTER2D_BWD=r|w|m at run time.
-#ifndef GSX_RASTER2D_BWD_DEFAULT
-#define GSX_RASTER2D_BWD_DEFAULT 'r'
-#endif
-bool raster2d_bwd_m_applies(const Raster2DArgs &a, bool has_abs);
-int raster2d_bwd_m_launch(const Raster2DArgs &a, hipStream_t stream);
 
 } // namespace gsx

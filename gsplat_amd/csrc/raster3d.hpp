@@ -40,12 +40,6 @@ struct Raster3DArgs {
     const uint8_t *masks;     // [I, tile_h, tile_w] or null (torch bool)
     const int32_t *isect_offsets; // [I, tile_h, tile_w]
     const int32_t *flatten_ids;   // [M]
-    // optional (cdim == 3 only): ONE 48-byte array-of-structures row per Gaussian row,
-    //   (x, y, conic a, conic b | conic c, opacity, colour 0, colour 1 | colour 2, -, -, -),
-    // the same values as means2d / conics / opacities / colors. A staging thread then needs three 16-byte loads from ONE row
-    // instead of four gathers from four arrays (c3 forward 0.203 -> 0.181 ms in the kernel harness, profiles/r10_ab.md): the
-    // SH forward of rasterization() writes the rows while it has the row's colours in registers (gsx_sh_fwd_rows)
-    const float *splat_rows;
     // forward outputs
     float *render_colors; // [I, H, W, cdim]
     float *render_alphas; // [I, H, W, 1]
@@ -84,9 +78,6 @@ struct Raster3DArgs {
     int32_t *seg_last;        // [item][256]  mode 2 out: last contributing list index, -1 = none
     // backward, dense layouts: workgroup -> tile map sorted by work (raster3d_bwd.hip: tile_order_*), or null = launch order
     const int32_t *tile_order;
-    // forward, dense layouts (one-wave kernel, raster3d_fwd_w.hip): [I * tile_h * tile_w] what each tile costs the backward - its
-    // list up to the last contributor, the quantity tile_order.hip sorts by - or null
-    int32_t *tile_cost;
 };
 
 // Block index -> (image, tile) with an XCD-aware remap: hardware places workgroup b on
@@ -155,13 +146,7 @@ __device__ __forceinline__ bool tile_context_seg(const Raster3DArgs &a, uint32_t
         // compositing pass: the workgroups behind the segment items take the SHORT tiles, whole list, straight into the
         // image (item = ~0) - one launch for everything, the long segments first
         if (a.seg_mode != 2u) return false;
-        uint32_t blk = block - (uint32_t)n_items;
-        if (a.tile_order) { // backward, one wave per unit: the short tiles longest-first too (tile_order.hip; per XCD range)
-            if (blk >= ((n_blocks + 7u) / 8u) * 8u) return false;
-            const uint32_t idx = xcd_remap(blk, n_blocks);
-            if (idx >= n_blocks) return false;
-            blk = (uint32_t)a.tile_order[idx];
-        }
+        const uint32_t blk = block - (uint32_t)n_items;
         if (blk >= n_blocks) return false;
         item       = 0xFFFFFFFFu;
         t.image_id = blk / tiles_per_image;
@@ -211,17 +196,9 @@ const int32_t *build_tile_order(const int32_t *isect_offsets, const int32_t *las
                                 uint32_t tile_w, uint32_t tile_h, uint32_t width, uint32_t height, uint32_t n_isects, void *ws,
                                 int64_t ws_bytes, hipStream_t stream, int *rc, void *zero_ptr = nullptr, int64_t zero_bytes = 0);
 
-// One wave per tile (raster3d_fwd_w.hip): <= 4 channels per launch, 16 x 16 tiles, no segments. GSX_RASTER3D_FWD=q|w at run time.
-// NOT the default: measured SLOWER than the four-waves-per-tile kernel (0.290 against 0.199 ms at c3, see raster3d_fwd_w.hip).
-#ifndef GSX_RASTER3D_FWD_DEFAULT
-#define GSX_RASTER3D_FWD_DEFAULT 'q'
-#endif
 // Wide colour rows (5 .. 32 channels per launch, 16 x 16 tiles, no segments) on the matrix cores: raster3d_fwd_m.hip.
-// GSX_RASTER3D_FWD_WIDE=q keeps the four-wave kernel.
 bool raster3d_fwd_m_applies(const Raster3DArgs &a);
 int raster3d_fwd_m_launch(const Raster3DArgs &a, hipStream_t stream);
-bool raster3d_fwd_w_applies(const Raster3DArgs &a);
-int raster3d_fwd_w_launch(const Raster3DArgs &a, hipStream_t stream);
 
 // ---- longest tiles first: csrc/tile_order.hip builds the order, the backward kernels read it through Raster3DArgs::tile_order ----
 // tile_context() through the order (dense layouts)

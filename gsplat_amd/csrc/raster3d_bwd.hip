@@ -19,7 +19,6 @@
 //      touches ~6 cache lines instead of 64. Measured on c3: the per-tensor layout (64 lines per instruction)
 //      cost 160 us of exposed L2-atomic time out of 707 us; the AoS flush costs < 5 us.
 #include <cstdlib>
-#include <cstring>
 
 #include "raster3d.hpp"
 #include "../../include/gsplat_amd.h"
@@ -745,11 +744,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
     float *s_w      = reinterpret_cast<float *>(s_aux + BATCH); // [SLOTS][4 quadrants][4 groups][GP]: (fac, w) per pixel
 
     TileCtx tc;
-    uint32_t seg_item = 0;
-    if (a.seg_mode != 0u) { // a launch over slices of long tile lists + the short tiles behind them (raster3d_seg.hip)
-        if (!tile_context_seg(a, blockIdx.x, tc, seg_item)) return;
-    } else if (a.tile_order ? !tile_context_ordered(a, blockIdx.x, tc) : !tile_context(a, blockIdx.x, tc)) return;
-    const bool in_segment = a.seg_mode != 0u && seg_item != 0xFFFFFFFFu;
+    if (a.tile_order ? !tile_context_ordered(a, blockIdx.x, tc) : !tile_context(a, blockIdx.x, tc)) return;
     if (a.masks && !a.masks[(size_t)tc.image_id * (a.tile_w * a.tile_h) + tc.tile_id]) return;
     const int32_t range_start = tc.range_start;
     if (tc.range_end <= range_start) return;
@@ -771,10 +766,8 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
         const bool inside  = prow >= 0;
         const size_t pix   = inside ? (size_t)prow : 0;
         const float T_fin  = inside ? 1.0f - a.render_alphas[pix] : 1.0f;
-        // a slice starts (back to front) from the transmittance at ITS end and from what lies behind it; the pre-pass stores
-        // both per pixel in the four-wave kernels' thread order: quadrant q, lane (raster3d_seg.hip: seg_bwd_prefix_kernel)
-        T[q]               = in_segment ? a.seg_T[(size_t)seg_item * 256 + (size_t)q * 64 + lane] : T_fin;
-        behind[q]          = in_segment ? a.seg_out[(size_t)seg_item * 256 + (size_t)q * 64 + lane] : 0.0f;
+        T[q]               = T_fin;
+        behind[q]          = 0.0f;
         bin_final[q]       = inside ? a.last_ids[pix] : -1;
 #pragma unroll
         for (int k = 0; k < CH; ++k) v_c[q][k] = (inside && k < (int)a.nch) ? a.v_render_colors[vrc_index(a, pix, a.ch_off + (uint32_t)k)] : 0.0f;
@@ -941,13 +934,6 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
     };
     auto fetch = [&](int32_t g, Fetched &f) {
         if (g < 0) return;
-        if (a.splat_rows) { // one 48-byte array-of-structures row (raster3d.hpp; cdim == 3): three 16-byte loads, one address
-            const v4f *rw = reinterpret_cast<const v4f *>(a.splat_rows) + 3 * (size_t)g;
-            const v4f r0 = rw[0], r1 = rw[1], r2 = rw[2];
-            f.xy = make_float2(r0.x, r0.y); f.ca = r0.z; f.cb = r0.w; f.cc = r1.x; f.opac = r1.y;
-            f.cv[0] = r1.z; f.cv[1] = CH > 1 ? r1.w : 0.0f; f.cv[2] = CH > 2 ? r2.x : 0.0f; f.cv[3] = 0.0f;
-            return;
-        }
         f.xy   = reinterpret_cast<const float2 *>(a.means2d)[g];
         f.opac = a.opacities[g];
         f.ca = a.conics[3 * (size_t)g]; f.cb = a.conics[3 * (size_t)g + 1]; f.cc = a.conics[3 * (size_t)g + 2];
@@ -1120,7 +1106,7 @@ raster3d_bwd_w_abs_kernel(Raster3DArgs a)
     raster3d_bwd_w_body<CH, true>(a);
 }
 
-// Variant T is the default where it applies; GSX_RASTER3D_BWD=r selects the reduction kernel (read once per process).
+// GSX_RASTER3D_BWD=r|t|w selects the kernel for <= 4 channels per launch (default GSX_RASTER3D_BWD_DEFAULT; read once per process).
 static char bwd_variant()
 {
     static const char v = [] {
@@ -1173,55 +1159,14 @@ int raster3d_bwd_t_launch_items(const Raster3DArgs &a, hipStream_t stream)
     return check_launch("raster3d_bwd_t(segments)");
 }
 bool raster3d_bwd_uses_variant_t() { return use_variant_t(); }
-bool raster3d_bwd_uses_variant_w() { return bwd_variant() == 'w'; }
-// variant W over the same item list (one wave per slice / short tile); a.nch <= 4, tile size 16, no absgrad
-int raster3d_bwd_w_launch_items(const Raster3DArgs &a, hipStream_t stream)
-{
-    const uint32_t grid = ((a.seg_grid + 7u) / 8u) * 8u;
-    if (grid == 0) return GSX_OK;
-    if (a.nch <= 1) raster3d_bwd_w_kernel<1><<<dim3(grid), dim3(64), BwdWCfg<1>::smem, stream>>>(a);
-    else if (a.nch <= 2) raster3d_bwd_w_kernel<2><<<dim3(grid), dim3(64), BwdWCfg<2>::smem, stream>>>(a);
-    else if (a.nch <= 3) raster3d_bwd_w_kernel<3><<<dim3(grid), dim3(64), BwdWCfg<3>::smem, stream>>>(a);
-    else raster3d_bwd_w4_kernel<<<dim3(grid), dim3(64), BwdWCfg<4>::smem, stream>>>(a);
-    return check_launch("raster3d_bwd_w(segments)");
-}
-
-// Five to eight channels: variant W takes them FOUR AT A TIME (the gradient of alpha is linear in the channels, so every launch
-// adds its share of the geometry gradients; first_chunk carries the alpha cotangent). Measured at c3 (profiles/r09_ab.md):
-// 8 channels 0.856 ms in two launches of W against 0.890 for one of the reduction kernel; 16 channels 1.70 against 1.33, 32
-// channels 3.45 against 2.48 - every launch walks the pixels again, and from three launches on that outweighs the cheaper sums.
-// Not with absgrad: sum |v_sigma g| over the pixels is not linear in the channels. GSX_BWD_W_WIDE=lo,hi overrides the range
-// (0,0 = never).
-static void bwd_w_wide_range(uint32_t &lo, uint32_t &hi)
-{
-    static const uint64_t v = [] {
-        uint32_t l = 0, h = 0; // off since the matrix-core kernel (raster3d_bwd_m.hip) takes 5 .. 32 channels
-        if (const char *e = getenv("GSX_BWD_W_WIDE")) {
-            l = (uint32_t)atoi(e);
-            const char *c = strchr(e, ',');
-            h = c ? (uint32_t)atoi(c + 1) : l;
-        }
-        return ((uint64_t)l << 32) | h;
-    }();
-    lo = (uint32_t)(v >> 32);
-    hi = (uint32_t)v;
-}
-static bool bwd_w_wide(const Raster3DArgs &a, bool has_abs)
-{
-    uint32_t lo, hi;
-    bwd_w_wide_range(lo, hi);
-    return !has_abs && a.cdim > 4 && a.tile_size == 16 && bwd_variant() == 'w' && a.cdim >= lo && a.cdim <= hi;
-}
-
 template <bool ABS>
 static int bwd_dispatch(Raster3DArgs a, hipStream_t stream)
 {
-    const uint32_t width = bwd_w_wide(a, ABS) ? 4u : 32u; // channels per launch
     uint32_t off = 0;
     bool first   = true;
     do {
         const uint32_t rem = a.cdim - off;
-        const uint32_t n   = rem > width ? width : rem;
+        const uint32_t n   = rem > 32 ? 32 : rem;
         a.ch_off           = off;
         a.nch              = n;
         a.first_chunk      = first ? 1u : 0u;
@@ -1282,45 +1227,8 @@ extern "C" int gsx_raster3d_bwd_ws(
 // gsx_raster3d_bwd_ws for gradient rows that are NOT zero-filled yet: the call fills v_rows_to_fill rows of row_stride floats
 // itself - inside the tile-order cost kernel when one is launched (a kernel short of memory work: 36 MB of zeros cost it ~2 us
 // where a fill kernel of its own takes 7.5), with a memset otherwise. v_rows_to_fill == 0: the caller filled them.
-static int raster3d_bwd_fill_impl(
-    const float *means2d, const float *conics, const float *colors, const float *opacities, const float *splat_rows,
-    const float *backgrounds, const uint8_t *masks, const int32_t *isect_offsets, const int32_t *flatten_ids,
-    const float *render_alphas, const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
-    uint32_t n_images, uint32_t n_isects, uint32_t cdim, uint32_t width, uint32_t height, uint32_t tile_size,
-    uint32_t tile_w, uint32_t tile_h, int has_abs, float *v_rows, uint32_t row_stride, int64_t v_rows_to_fill,
-    int64_t v_colors_pixel_stride, int64_t v_colors_channel_stride, void *workspace, int64_t workspace_bytes, void *stream);
 extern "C" int gsx_raster3d_bwd_fill(
     const float *means2d, const float *conics, const float *colors, const float *opacities,
-    const float *backgrounds, const uint8_t *masks, const int32_t *isect_offsets, const int32_t *flatten_ids,
-    const float *render_alphas, const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
-    uint32_t n_images, uint32_t n_isects, uint32_t cdim, uint32_t width, uint32_t height, uint32_t tile_size,
-    uint32_t tile_w, uint32_t tile_h, int has_abs, float *v_rows, uint32_t row_stride, int64_t v_rows_to_fill,
-    int64_t v_colors_pixel_stride, int64_t v_colors_channel_stride, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    return raster3d_bwd_fill_impl(means2d, conics, colors, opacities, nullptr, backgrounds, masks, isect_offsets, flatten_ids,
-                                  render_alphas, last_ids, v_render_colors, v_render_alphas, n_images, n_isects, cdim, width, height,
-                                  tile_size, tile_w, tile_h, has_abs, v_rows, row_stride, v_rows_to_fill, v_colors_pixel_stride,
-                                  v_colors_channel_stride, workspace, workspace_bytes, stream);
-}
-// gsx_raster3d_bwd_fill with the Gaussians' 48-byte array-of-structures rows beside the four arrays (cdim == 3, no absgrad;
-// raster3d.hpp: Raster3DArgs::splat_rows). Only the one-wave-per-tile kernel reads them; every other kernel ignores the pointer.
-extern "C" int gsx_raster3d_bwd_fill_rows(
-    const float *means2d, const float *conics, const float *colors, const float *opacities, const float *splat_rows,
-    const float *backgrounds, const uint8_t *masks, const int32_t *isect_offsets, const int32_t *flatten_ids,
-    const float *render_alphas, const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
-    uint32_t n_images, uint32_t n_isects, uint32_t cdim, uint32_t width, uint32_t height, uint32_t tile_size,
-    uint32_t tile_w, uint32_t tile_h, int has_abs, float *v_rows, uint32_t row_stride, int64_t v_rows_to_fill,
-    int64_t v_colors_pixel_stride, int64_t v_colors_channel_stride, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    GSX_REQUIRE(!splat_rows || cdim == 3, "gsx_raster3d_bwd_fill_rows: the rows hold three colours; cdim is %u", cdim);
-    GSX_REQUIRE(!splat_rows || (reinterpret_cast<uintptr_t>(splat_rows) & 15u) == 0, "gsx_raster3d_bwd_fill_rows: rows must be 16-byte aligned");
-    return raster3d_bwd_fill_impl(means2d, conics, colors, opacities, splat_rows, backgrounds, masks, isect_offsets, flatten_ids,
-                                  render_alphas, last_ids, v_render_colors, v_render_alphas, n_images, n_isects, cdim, width, height,
-                                  tile_size, tile_w, tile_h, has_abs, v_rows, row_stride, v_rows_to_fill, v_colors_pixel_stride,
-                                  v_colors_channel_stride, workspace, workspace_bytes, stream);
-}
-static int raster3d_bwd_fill_impl(
-    const float *means2d, const float *conics, const float *colors, const float *opacities, const float *splat_rows,
     const float *backgrounds, const uint8_t *masks, const int32_t *isect_offsets, const int32_t *flatten_ids,
     const float *render_alphas, const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
     uint32_t n_images, uint32_t n_isects, uint32_t cdim, uint32_t width, uint32_t height, uint32_t tile_size,
@@ -1349,7 +1257,7 @@ static int raster3d_bwd_fill_impl(
     Raster3DArgs a{};
     a.n_images = n_images; a.n_isects = n_isects; a.width = width; a.height = height;
     a.tile_size = tile_size; a.tile_w = tile_w; a.tile_h = tile_h; a.cdim = cdim;
-    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities; a.splat_rows = splat_rows;
+    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
     a.backgrounds = backgrounds; a.masks = masks; a.isect_offsets = isect_offsets; a.flatten_ids = flatten_ids;
     a.render_alphas = const_cast<float *>(render_alphas); a.last_ids = const_cast<int32_t *>(last_ids);
     a.v_render_colors = v_render_colors; a.v_render_alphas = v_render_alphas;
@@ -1358,11 +1266,10 @@ static int raster3d_bwd_fill_impl(
         GSX_REQUIRE(v_colors_channel_stride >= 0, "gsx_raster3d_bwd_ws: negative channel stride");
         a.vrc_strided = 1u; a.vrc_ps = v_colors_pixel_stride; a.vrc_cs = v_colors_channel_stride;
     }
-    // the launches that read the order: variant W (also with absgrad, and four channels at a time), variant T
+    // the launches that read the order: variant W (also with absgrad), variant T, the matrix-core kernel
     a.nch = cdim > 32 ? 32 : cdim; // what the first launch will see (bwd_dispatch sets it per chunk)
     const bool wide_m = cdim > 4 && bwd_variant() != 'r' && raster3d_bwd_m_applies(a, has_abs != 0);
-    if (wide_m || (bwd_variant() == 'w' ? (tile_size == 16 && (cdim <= 4 || bwd_w_wide(a, has_abs != 0)))
-                                        : (!has_abs && cdim <= 4 && bwd_variant() != 'r'))) {
+    if (wide_m || (bwd_variant() == 'w' ? (tile_size == 16 && cdim <= 4) : (!has_abs && cdim <= 4 && bwd_variant() != 'r'))) {
         int rc       = GSX_OK;
         const bool in_kernel = fill_bytes > 0 && (reinterpret_cast<uintptr_t>(v_rows) & 15u) == 0;
         a.tile_order = a.sp_active_tiles ? nullptr

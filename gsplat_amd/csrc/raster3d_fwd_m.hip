@@ -217,29 +217,12 @@ __global__ void __launch_bounds__(256) raster3d_fwd_m_kernel(const Raster3DArgs 
         }
 }
 
-// GSX_RASTER3D_FWD_WIDE=q keeps the four-wave kernel for wide colour rows (A/B; read once per process)
-static bool fwd_m_enabled()
-{
-    static const bool on = [] {
-        const char *e = getenv("GSX_RASTER3D_FWD_WIDE");
-        return !(e && (e[0] == 'q' || e[0] == 'Q' || e[0] == '0'));
-    }();
-    return on;
-}
-static uint32_t fwd_m_min_channels() // GSX_RASTER3D_FWD_WIDE_MIN overrides (A/B)
-{
-    static const uint32_t v = [] {
-        const char *e = getenv("GSX_RASTER3D_FWD_WIDE_MIN");
-        const int x   = e ? atoi(e) : 17;
-        return (uint32_t)(x > 5 ? x : 5);
-    }();
-    return v;
-}
+// from 17 channels on (two column blocks): at 5 / 8 / 12 channels the four-wave kernel is the faster one (0.25 / 0.28 / 0.33
+// against 0.34 / 0.35 / 0.38 ms at c3), at 16 they tie (0.38), at 32 this one wins (0.445 against 0.653; profiles/r09_ab.md)
+constexpr uint32_t kFwdMMinChannels = 17;
 bool raster3d_fwd_m_applies(const Raster3DArgs &a)
 {
-    // from 17 channels on (two column blocks): at 5 / 8 / 12 channels the four-wave kernel is the faster one (0.25 / 0.28 / 0.33
-    // against 0.34 / 0.35 / 0.38 ms at c3), at 16 they tie (0.38), at 32 this one wins (0.445 against 0.653; profiles/r09_ab.md)
-    return fwd_m_enabled() && a.tile_size == 16 && a.nch >= fwd_m_min_channels() && a.nch <= 32 && a.seg_mode == 0 && a.seg_len == 0;
+    return a.tile_size == 16 && a.nch >= kFwdMMinChannels && a.nch <= 32 && a.seg_mode == 0 && a.seg_len == 0;
 }
 int raster3d_fwd_m_launch(const Raster3DArgs &a, hipStream_t stream)
 {

@@ -31,38 +31,7 @@ namespace gsx {
 int raster3d_fwd_launch_chunk(const Raster3DArgs &a, hipStream_t stream);   // raster3d_fwd.hip
 int raster3d_bwd_prepass_launch(const Raster3DArgs &a, hipStream_t stream); // raster3d_fwd.hip (forward kernel, PRE = true)
 int raster3d_bwd_t_launch_items(const Raster3DArgs &a, hipStream_t stream); // raster3d_bwd.hip
-int raster3d_bwd_w_launch_items(const Raster3DArgs &a, hipStream_t stream); // raster3d_bwd.hip
 bool raster3d_bwd_uses_variant_t();
-bool raster3d_bwd_uses_variant_w();
-
-// Slice length of the BACKWARD for a forward slice length: the one-wave-per-tile kernel (variant W) walks a slice as ONE
-// instruction stream, so its slices are half as long as those of the four-wave kernels (the critical path of a launch is
-// its longest unit of work); the pre-pass costs the same either way (it evaluates every entry of the long lists once).
-// Garden x25, backward in ms (profiles/r09_ab.md): slices of 1024 0.863, 512 0.634 - 0.653, 256 0.667 - 0.698; variant T on
-// slices of 1024: 0.647 - 0.656. GSX_BWD_SEG_DIV overrides the divisor (A/B).
-// Which kernel walks the slices: variant T (four waves per unit) unless GSX_RASTER3D_BWD_SEG=w. Variant W over half-length
-// slices ties it on the garden x25 scene (0.645 against 0.646 ms) and LOSES on the 49 M-Gaussian scene of the reference's
-// profiling table (7.1 M intersections: 1.21 against 0.89 ms; slices of 1024 / 256: 1.12 / 1.27) - profiles/r09_ab.md #40.
-static bool seg_bwd_on_variant_w()
-{
-    static const bool w = [] {
-        const char *e = getenv("GSX_RASTER3D_BWD_SEG");
-        return e && e[0] == 'w';
-    }();
-    return w && raster3d_bwd_uses_variant_w();
-}
-
-static uint32_t bwd_slice_len(uint32_t seg_len)
-{
-    if (!seg_bwd_on_variant_w() || seg_len == 0) return seg_len;
-    static const uint32_t div = [] {
-        const char *e = getenv("GSX_BWD_SEG_DIV");
-        const int v   = e ? atoi(e) : 2;
-        return (uint32_t)(v >= 1 ? v : 1);
-    }();
-    const uint32_t l = seg_len / div;
-    return l < 256u ? 256u : l;
-}
 
 struct SegHeader { // device memory, zeroed before every use
     int32_t n_items, n_long, pad[2];
@@ -300,13 +269,11 @@ extern "C" int64_t gsx_raster3d_seg_workspace_bytes(int64_t n_isects, uint32_t n
     return seg_layout(n_isects, n_images * tile_w * tile_h, nch_max, seg_len, nullptr, nullptr) + 512;
 }
 
-// workspace of gsx_raster3d_bwd_seg (its slices may be shorter than the forward's: bwd_slice_len)
+// workspace of gsx_raster3d_bwd_seg: the same plan over the same slices as the forward's
 extern "C" int64_t gsx_raster3d_bwd_seg_workspace_bytes(int64_t n_isects, uint32_t n_images, uint32_t tile_w, uint32_t tile_h,
                                                         uint32_t cdim, uint32_t seg_len)
 {
-    // + the longest-first order of the short tiles (variant W: one wave per unit of work, tile_order.hip)
-    return gsx_raster3d_seg_workspace_bytes(n_isects, n_images, tile_w, tile_h, cdim, bwd_slice_len(seg_len))
-           + tile_order_workspace_bytes(n_images, tile_w, tile_h) + 256;
+    return gsx_raster3d_seg_workspace_bytes(n_isects, n_images, tile_w, tile_h, cdim, seg_len);
 }
 
 extern "C" int gsx_raster3d_fwd_seg(
@@ -397,8 +364,6 @@ static int raster3d_bwd_seg_impl(
                                 tile_w, tile_h, 0, v_rows, row_stride, stream);
     GSX_REQUIRE(seg_len >= 256, "gsx_raster3d_bwd_seg: seg_len must be >= 256, got %u", seg_len);
     if (n_isects == 0) return GSX_OK;
-    const uint32_t fwd_seg_len = seg_len;
-    seg_len = bwd_slice_len(seg_len); // workspace: gsx_raster3d_bwd_seg_workspace_bytes
     GSX_REQUIRE(v_rows && row_stride >= 6u + cdim, "gsx_raster3d_bwd_seg: gradient rows missing / too narrow");
     GSX_REQUIRE(means2d && conics && colors && opacities && flatten_ids && render_alphas && last_ids && v_render_colors
                 && isect_offsets, "gsx_raster3d_bwd_seg: null input");
@@ -423,13 +388,13 @@ static int raster3d_bwd_seg_impl(
         return GSX_ERR_WORKSPACE;
     }
     // The forward's workspace over the same lists (gsx_raster3d_bwd_seg_reuse): its plan IS this launch's plan and its
-    // per-slice sums replace the pre-pass - when the backward cuts its slices as long as the forward did (variant T)
+    // per-slice sums replace the pre-pass
     SegPlan pf{};
     bool reuse = false;
-    if (fwd_workspace && seg_len == fwd_seg_len) {
+    if (fwd_workspace) {
         unsigned char *fbase = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(fwd_workspace) + 255) & ~(uintptr_t)255);
         const int64_t need = (fbase - reinterpret_cast<const unsigned char *>(fwd_workspace))
-                             + seg_layout(n_isects, n_blocks, cdim, fwd_seg_len, fbase, &pf);
+                             + seg_layout(n_isects, n_blocks, cdim, seg_len, fbase, &pf);
         if (need > fwd_workspace_bytes) {
             set_last_error("gsx_raster3d_bwd_seg_reuse: forward workspace too small for these lists (not the forward call's?)");
             return GSX_ERR_WORKSPACE;
@@ -456,17 +421,7 @@ static int raster3d_bwd_seg_impl(
     // the slices first, the short tiles behind them. The short-tile range must hold round8(n_blocks) workgroups whatever the
     // device-side item count is (xcd_remap is a bijection over round8(n_blocks) slots only)
     a.seg_mode = 2; a.seg_grid = p.max_items + ((n_blocks + 7u) / 8u) * 8u;
-    if (seg_bwd_on_variant_w()) {
-        // one wave per unit: a short tile of up to seg_cut entries started late is the launch's tail - take them longest-first
-        // (the order lives behind the segment plan in the workspace, when the caller sized it with the backward's own function)
-        unsigned char *ord = base + align256(seg_layout(n_isects, n_blocks, cdim, seg_len, base, nullptr));
-        const int64_t left = workspace_bytes - (ord - reinterpret_cast<unsigned char *>(workspace));
-        int orc = GSX_OK;
-        a.tile_order = build_tile_order(isect_offsets, last_ids, n_images, tile_size, tile_w, tile_h, width, height, n_isects, ord,
-                                        left, s, &orc);
-        if (orc != GSX_OK) return orc;
-    }
-    rc = seg_bwd_on_variant_w() ? raster3d_bwd_w_launch_items(a, s) : raster3d_bwd_t_launch_items(a, s);
+    rc = raster3d_bwd_t_launch_items(a, s);
     if (rc != GSX_OK) return rc;
     return check_launch("raster3d_bwd_seg");
 }

@@ -276,20 +276,3 @@ def test_segmented_backward_from_the_forward_workspace_equals_the_prepass(G, kin
         assert_grad_close(a.cpu(), c.cpu(), name=f"{kind} reuse vs pre-pass v_{nm}")
         assert_grad_close(a.cpu(), b.cpu(), name=f"{kind} reuse, second backward v_{nm}")
     del rc
-
-
-def test_segmented_backward_on_the_one_wave_kernel():
-    """GSX_RASTER3D_BWD_SEG=w (read once per process): the slices walked by variant W - half-length slices, short tiles
-    longest-first - instead of the default four-wave kernel; the same comparisons as above, in a subprocess."""
-    import os
-    import subprocess
-    import sys
-
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GSX_RASTER3D_BWD_SEG="w")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_segments.py"), "-q", "-m", "gpu", "-x",
-                        "-p", "no:cacheprovider", "-k", "segmented_backward_matches_per_tile_walk and (mixed or opaque) and not 1]"],
-                       capture_output=True, text=True, env=env, timeout=900, cwd=root)
-    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

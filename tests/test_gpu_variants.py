@@ -1,10 +1,12 @@
 """GPU: alternative kernel variants selected by environment switches must reproduce the default kernels.
 
-GSX_RASTER3D_BWD=r — compositing backward with wave reductions (csrc/raster3d_bwd.hip) instead of the default transposed
-per-Gaussian accumulation (variant T; used for <= 4 channels per launch, 16 x 16 tiles, no absgrad). The switch is read
-once per process, so the other kernel runs in a subprocess on the same seeded scenes and its gradients are compared with
-the default kernel's (scale-relative: the sums are taken in a different order). Both kernels are also what the
-oracle-parity tests exercise: T through every default test, R through absgrad / wide-channel / small-tile cases."""
+GSX_RASTER3D_BWD=r|t|w — the 3DGS compositing backward with wave reductions (R), the transposed per-Gaussian accumulation
+(T) or one wave per tile (W, the default for <= 4 channels per launch and 16 x 16 tiles; csrc/raster3d_bwd.hip).
+GSX_RASTER2D_BWD=r — the 2DGS compositing backward with wave reductions instead of the default one wave per half tile
+(csrc/raster2d.hip). Each switch is read once per process, so the other kernel runs in a subprocess on the same seeded
+scenes and its gradients are compared with the default kernel's (scale-relative: the sums are taken in a different order).
+Every kernel is also what the default dispatch reaches for some inputs: R for absgrad / wide-channel / small-tile cases, T
+for the slices of long tile lists (tests/test_gpu_segments.py)."""
 import os
 import subprocess
 import sys
@@ -93,35 +95,6 @@ def test_raster3d_bwd_variants_match_the_default(variant):
                               name=f"case {i} v_{k}")
 
 
-@pytest.mark.parametrize("variant", ["w", "h"])
-def test_raster3d_fwd_one_wave_per_tile_matches_the_default(variant):
-    """GSX_RASTER3D_FWD=w / h: the forward with one wave per tile / per half tile (csrc/raster3d_fwd_w.hip; not the default) against
-    the four-waves-per-tile kernel (csrc/raster3d_fwd.hip). Same staged form and the same per-pixel arithmetic in the same
-    order: the renders must agree to rounding (a different cull never changes a result), and so must the gradients, which
-    start from the forward's state."""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a ROCm GPU")
-    assert os.environ.get("GSX_RASTER3D_FWD", "") == "", "run this test with the default kernel selection"
-    import gsplat_amd
-    from _util import assert_close_ratio
-
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "t.npz")
-        code = _SCRIPT % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
-        r = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True,
-                           env=dict(os.environ, GSX_RASTER3D_FWD=variant), timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        alt = dict(np.load(path))
-    for i, case in enumerate(CASES):
-        ref = run_case(gsplat_amd, case)
-        assert_close_ratio(torch.from_numpy(alt[f"{i}_render"]), torch.from_numpy(ref["render"]), 1e-6, 1e-6, max_bad_ratio=1e-5,
-                           name=f"case {i} render")
-        for k, v in ref.items():
-            if k != "render":
-                assert_grad_close(torch.from_numpy(alt[f"{i}_{k}"]), torch.from_numpy(v), rel=3e-4, max_bad_ratio=1e-5,
-                                  name=f"case {i} v_{k}")
-
-
 _SCRIPT_2DGS = r'''
 import sys, numpy as np, torch
 sys.path.insert(0, %(root)r); sys.path.insert(0, %(tests)r)
@@ -153,12 +126,11 @@ def run_case_2dgs(G):
     return out
 
 
-@pytest.mark.parametrize("variant", ["r", "w", "m"])
+@pytest.mark.parametrize("variant", ["r"])
 def test_raster2d_bwd_variants_match_the_default(variant):
     """The default is one wave per HALF tile (csrc/raster2d.hip: raster2d_bwd_w_kernel<.., 2>). GSX_RASTER2D_BWD=r (the four-wave
-    reduction kernel), =w (the same kernel as the default, one wave per tile) and =m (csrc/raster2d_bwd_m.hip: the
-    per-(tile, surfel) sums as one fp32-MFMA product per four surfels) - both measured and not the default - must give the
-    gradients of the reduction kernel: RGB+ED with distortion loss and SH, long lists, a single depth channel."""
+    reduction kernel, which the default dispatch takes for absgrad, tiles other than 16 and more than four channels) must give
+    the same gradients: RGB+ED with distortion loss and SH, long lists, a single depth channel."""
     if not torch.cuda.is_available():
         pytest.skip("needs a ROCm GPU")
     assert os.environ.get("GSX_RASTER2D_BWD", "") == ""
@@ -177,6 +149,6 @@ def test_raster2d_bwd_variants_match_the_default(variant):
         if k.endswith("_render"):
             assert np.array_equal(alt[k], v), k
         else:
-            # four pixels are summed per lane before ONE wave reduction (the default reduces per quadrant): another association
+            # two pixels are summed per lane before ONE wave reduction (the reduction kernel reduces per quadrant): another association
             # order of the same fp32 sums; the distortion terms of the depth-only case cancel strongly (1.3e-3 of scale on 3 of 12000)
             assert_grad_close(torch.from_numpy(alt[k]), torch.from_numpy(v), rel=2e-3, max_bad_ratio=1e-3, name=k)
