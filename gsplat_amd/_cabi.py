@@ -169,26 +169,44 @@ _profile = None  # list of (entry point, start event, end event) while profiling
 _profile_only = None  # optional set of entry points to record (None = all)
 
 
+def torch_lib_path() -> str:
+    """libgsplat_amd_torch.so, linked against the kernel library in use: GSPLAT_AMD_TORCH_LIB, else the one named after
+    GSPLAT_AMD_LIB (tools/mkvariant.sh: libgsplat_amd_<name>.so -> libgsplat_amd_torch_<name>.so next to it), else the
+    default build's."""
+    if os.environ.get("GSPLAT_AMD_TORCH_LIB"):
+        return os.environ["GSPLAT_AMD_TORCH_LIB"]
+    d, base = os.path.split(lib_path())
+    if not (base.startswith("libgsplat_amd") and base.endswith(".so")):
+        raise ImportError(f"gsplat_amd: {_LIB_ENV}={lib_path()} does not follow the naming rule libgsplat_amd*.so; set "
+                          "GSPLAT_AMD_TORCH_LIB to the libgsplat_amd_torch*.so linked against it")
+    return os.path.join(d, "libgsplat_amd_torch" + base[len("libgsplat_amd"):])
+
+
+def check_single_kernel_library() -> None:
+    """After libgsplat_amd_torch.so is loaded: its compiled op bodies must call the same kernel library as this module (an
+    A/B build with a torch library linked against another one would silently run the other's kernels)."""
+    with open("/proc/self/maps") as f:
+        libs = {os.path.realpath(ln.split(None, 5)[5].strip()) for ln in f if len(ln.split(None, 5)) == 6}
+    kernels = {p for p in libs if os.path.basename(p).startswith("libgsplat_amd") and "_torch" not in os.path.basename(p)}
+    if kernels != {os.path.realpath(lib_path())}:
+        raise ImportError(f"gsplat_amd: {torch_lib_path()} is linked against {sorted(kernels - {os.path.realpath(lib_path())})}, "
+                          f"not {lib_path()}; build the matching torch library (tools/mkvariant.sh, make SUFFIX=... torch)")
+
+
 _torch_lib = None
 
 
-def _compiled_ops_lib():
-    """libgsplat_amd_torch.so (csrc/torch_ops.cpp), when it is loaded: its op bodies call the C-ABI without passing through
-    call() below, so they carry their own event-pair hooks."""
+def torch_lib() -> ctypes.CDLL:
+    """libgsplat_amd_torch.so (csrc/torch_ops.cpp; gsplat_amd._ops loads it at import): the long-tile hint of its compositing
+    body, and the event-pair hooks of its op bodies, which call the C-ABI without passing through call() below."""
     global _torch_lib
     if _torch_lib is None:
-        path = os.environ.get("GSPLAT_AMD_TORCH_LIB") or os.path.join(_HERE, "csrc", "libgsplat_amd_torch.so")
-        _torch_lib = False
-        if os.path.exists(path):
-            try:
-                lib = ctypes.CDLL(path)
-                lib.gsx_torch_profile_begin.argtypes = [ctypes.c_char_p]
-                lib.gsx_torch_profile_begin.restype = None
-                lib.gsx_torch_profile_end.restype = ctypes.c_char_p
-                _torch_lib = lib
-            except (OSError, AttributeError):
-                _torch_lib = False
-    return _torch_lib or None
+        lib = ctypes.CDLL(torch_lib_path())
+        lib.gsx_torch_set_long_tile_hint.argtypes, lib.gsx_torch_set_long_tile_hint.restype = [ctypes.c_int64], None
+        lib.gsx_torch_profile_begin.argtypes, lib.gsx_torch_profile_begin.restype = [ctypes.c_char_p], None
+        lib.gsx_torch_profile_end.restype = ctypes.c_char_p
+        _torch_lib = lib
+    return _torch_lib
 
 
 def profile_begin(only=None) -> None:
@@ -198,9 +216,7 @@ def profile_begin(only=None) -> None:
     global _profile, _profile_only
     _profile = []
     _profile_only = None if only is None else frozenset(only)
-    lib = _compiled_ops_lib()
-    if lib is not None:
-        lib.gsx_torch_profile_begin(" ".join(sorted(_profile_only or ())).encode())
+    torch_lib().gsx_torch_profile_begin(" ".join(sorted(_profile_only or ())).encode())
 
 
 def profile_end() -> dict:
@@ -211,11 +227,9 @@ def profile_end() -> dict:
     out = {}
     for name, a, b in rec:
         out.setdefault(name, []).append(a.elapsed_time(b))
-    lib = _compiled_ops_lib()
-    if lib is not None:  # the calls made by the compiled op bodies
-        for line in lib.gsx_torch_profile_end().decode().splitlines():
-            name, ms = line.split()
-            out.setdefault(name, []).append(float(ms))
+    for line in torch_lib().gsx_torch_profile_end().decode().splitlines():  # the calls made by the compiled op bodies
+        name, ms = line.split()
+        out.setdefault(name, []).append(float(ms))
     return out
 
 

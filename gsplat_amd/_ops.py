@@ -3,6 +3,10 @@
 Importing this module defines the reference's operator schemas (verbatim from
 ``gsplat/cuda/ext.cpp:983-1213`` for the ops on the hot path) in the ``gsplat`` namespace and
 registers implementations for the ``CUDA`` dispatch key (HIP tensors carry that key on ROCm).
+Every op has exactly one body: six forward stage ops on the critical host path of rasterization() /
+rasterization_2dgs() (projection_ewa_3dgs_fused / _packed, intersect_offset, rasterize_to_pixels_3dgs,
+projection_2dgs_fused, rasterize_to_pixels_2dgs) are C++ in ``csrc/torch_ops.cpp`` (libgsplat_amd_torch.so,
+loaded at import and required); every other op, the backward ones included, is a function of this file.
 Each implementation owns what the reference's C++ host op owns — shape checks, output
 allocation from the caching allocator, stream lookup, error translation — and hands raw device
 pointers to ``libgsplat_amd.so`` (``include/gsplat_amd.h``). Autograd is attached separately
@@ -32,31 +36,25 @@ _lib_impl = torch.library.Library(NS, "IMPL", "CUDA")
 _lib_impl_autograd = torch.library.Library(NS, "IMPL", "AutogradCUDA")  # whole-pipeline ops only (see COMPOSITE_SCHEMAS)
 
 
-
-def _load_torch_classes() -> Optional[str]:
-    """Load libgsplat_amd_torch.so (csrc/torch_classes.cpp): the torch custom classes that the composite schemas below
-    name by type (``torch.classes.gsplat.UnscentedTransformParameters`` ...). Returns None on success, else the reason
-    the composite ops are not defined (every stage op stays available without it)."""
-    import os
-
-    path = os.environ.get("GSPLAT_AMD_TORCH_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc",
-                                                                  "libgsplat_amd_torch.so")
-    try:
-        torch.classes.gsplat.UnscentedTransformParameters  # already registered (e.g. by the reference's own extension)
-        return None
-    except RuntimeError:
-        pass
+def _load_torch_lib() -> None:
+    """Load libgsplat_amd_torch.so (csrc/torch_classes.cpp + csrc/torch_ops.cpp): the torch custom classes that the composite
+    schemas below name by type (``torch.classes.gsplat.UnscentedTransformParameters`` ...), the compiled CUDA-key bodies of
+    the forward stage ops on the critical host path (the ops of SCHEMAS without a body in this file), the halves of the
+    fused intersection and the notes. Required: those ops have no other body."""
+    path = _cabi.torch_lib_path()
+    hint = "build it with `make -C gsplat_amd/csrc torch`"
     if not os.path.exists(path):
-        return f"{path} not built (make -C gsplat_amd/csrc torch)"
+        raise ImportError(f"gsplat_amd: {path} not found; {hint}")
     try:
         torch.classes.load_library(path)
     except OSError as e:
-        return f"cannot load {path}: {e}"
-    _read_compiled_ops(path)
-    return None
+        raise ImportError(f"gsplat_amd: cannot load {path} ({e}); {hint}") from None
+    _cabi.check_single_kernel_library()
 
 
-_COMPILED_ISECT = False  # torch.ops.gsplat_amd.isect_fused_{begin,finish} available (set by _read_compiled_ops)
+_load_torch_lib()
+COMPOSITE_UNAVAILABLE = None  # why the composite ops would be undefined: never, the torch library is required (kept for callers)
+_set_hint_compiled = _cabi.torch_lib().gsx_torch_set_long_tile_hint
 
 # ---- longest tile list: a hint from the orchestrator to the compositing ops ------------------------------------------------
 # rendering.py learns the longest tile list from the intersection's pinned host words; the reference's op schemas have no
@@ -71,7 +69,6 @@ def _seg_cut(n_isects: int, n_images: int, tw: int, th: int) -> int:
     return _cabi._lib.gsx_raster3d_seg_cut(int(n_isects), int(n_images), int(tw), int(th), SEG_LEN) if SEG_LEN > 0 else 1 << 62
 
 _hint = __import__("threading").local()
-_set_hint_compiled = None  # gsx_torch_set_long_tile_hint of libgsplat_amd_torch.so (the compiled op bodies read it)
 
 
 def long_tile_hint() -> int:
@@ -85,10 +82,10 @@ def long_tile_hint_of_call() -> int:
 
 
 def set_long_tile_hint(longest: int) -> None:
-    """Called by the WRAPPER around an op call (and with 0 in its finally block)."""
+    """Called by the WRAPPER around an op call (and with 0 in its finally block). The compiled compositing forward reads its
+    own copy (gsx_torch_set_long_tile_hint), the Python backward bodies this one."""
     _hint.longest = _hint.of_call = int(longest)
-    if _set_hint_compiled is not None:
-        _set_hint_compiled(int(longest))
+    _set_hint_compiled(int(longest))
 
 
 def _consume_long_tile_hint() -> int:
@@ -101,99 +98,25 @@ def _consume_long_tile_hint() -> int:
 # Stage-level callers (isect_tiles -> isect_offset_encode -> rasterize_to_pixels without rasterization() in between) have no
 # orchestrator to carry the hint: the intersection notes the longest list of its result and a compositing call without a hint
 # looks its flatten_ids up. A note is keyed by the IDENTITY of the tensor's storage, never by an address the allocator may hand
-# out again (csrc/torch_ops.cpp keeps the notes - weak references to the StorageImpl - when the compiled shim is loaded, so that
-# Python and compiled bodies see the same ones; the fallback below keeps the noted tensors of its 16-entry ring alive instead).
-_notes_compiled = False
-_notes_py: list = []  # [((StorageImpl address, storage offset, numel), the tensor (kept alive), longest)], newest last
-_notes_lock = __import__("threading").Lock()
-
-
-def _note_key(t: Tensor):
-    st = t.untyped_storage()
-    return (st._cdata, t.storage_offset(), t.numel())
-
-
-def _note_longest(flatten_ids: Tensor, longest: int) -> None:
-    if flatten_ids.numel() == 0:
-        return
-    if _notes_compiled:
-        torch.ops.gsplat_amd.note_longest(flatten_ids, int(longest))
-        return
-    # fallback (no compiled shim, or GSPLAT_AMD_LIB set): keyed by the StorageImpl's address + view, with a STRONG reference
-    # to the tensor in a 16-entry ring - the address cannot be handed out again while its note is alive, and the note does not
-    # depend on torch preserving the Python wrapper of a storage between calls
-    key = _note_key(flatten_ids)
-    with _notes_lock:
-        _notes_py[:] = [e for e in _notes_py if e[0] != key][-15:]
-        _notes_py.append((key, flatten_ids, int(longest)))
+# out again; csrc/torch_ops.cpp keeps the notes (weak references to the StorageImpl), for the compiled and the Python bodies.
 
 
 def _lookup_longest(flatten_ids: Tensor) -> int:
-    if _notes_compiled:
-        return int(torch.ops.gsplat_amd.lookup_longest(flatten_ids))
-    if flatten_ids.numel() == 0:
-        return 0
-    key = _note_key(flatten_ids)
-    with _notes_lock:
-        for k, _keep, longest in _notes_py:
-            if k == key:
-                return longest
-    return 0
+    return int(torch.ops.gsplat_amd.lookup_longest(flatten_ids))
 
 
 # The segment workspace of a compositing forward, for the backward over the same lists (csrc/raster3d_seg.hip:
 # gsx_raster3d_bwd_seg_reuse). The notes live in libgsplat_amd_torch.so (csrc/torch_ops.cpp: keyed by the identity of last_ids,
-# shared with the compiled op bodies); without the compiled shim the backward simply runs its pre-pass.
+# written by the compiled forward body).
 _SEG_REUSE = os.environ.get("GSPLAT_AMD_SEG_REUSE", "1") not in ("0", "")
 
 
-def _note_seg_workspace(last_ids: Tensor, ws: Tensor, n_isects: int, D: int, inputs) -> None:
+def _lookup_seg_workspace(last_ids: Tensor, n_isects: int, D: int, inputs) -> Optional[Tensor]:
     """`inputs`: (means2d, conics, colors, opacities, isect_offsets, flatten_ids) as the op received them - the note only serves
     a backward that brings the same tensors, unwritten since (address + version counter)."""
-    if _SEG_REUSE and _notes_compiled and hasattr(torch.ops.gsplat_amd, "note_seg_workspace"):
-        torch.ops.gsplat_amd.note_seg_workspace(last_ids, ws, int(n_isects), int(D), SEG_LEN, list(inputs))
-
-
-def _lookup_seg_workspace(last_ids: Tensor, n_isects: int, D: int, inputs) -> Optional[Tensor]:
-    if _SEG_REUSE and _notes_compiled and hasattr(torch.ops.gsplat_amd, "lookup_seg_workspace"):
+    if _SEG_REUSE:
         return torch.ops.gsplat_amd.lookup_seg_workspace(last_ids, int(n_isects), int(D), SEG_LEN, list(inputs))
     return None
-
-
-COMPILED_OPS: frozenset = frozenset()  # ops whose CUDA-key body is C++ (csrc/torch_ops.cpp) rather than a function of this file
-
-
-def _read_compiled_ops(path: str) -> None:
-    """libgsplat_amd_torch.so also carries compiled op bodies (csrc/torch_ops.cpp: TORCH_LIBRARY_IMPL(gsplat, CUDA) for the
-    hot stage ops, INTEGRATION.md route B). It names them through gsx_torch_compiled_ops(); _register() below keeps the
-    Python body of every OTHER op. GSPLAT_AMD_COMPILED_OPS=0 puts the Python bodies back (A/B of the host overhead)."""
-    global COMPILED_OPS
-    import ctypes
-
-    global _notes_compiled
-    _notes_compiled = hasattr(torch.ops, "gsplat_amd") and hasattr(torch.ops.gsplat_amd, "note_longest")
-    if os.environ.get("GSPLAT_AMD_LIB"):
-        # An A/B build of the kernel library is in use (tools/mkvariant.sh): the compiled bodies are linked against the
-        # DEFAULT libgsplat_amd.so and would silently run its kernels instead - keep every op on the ctypes path.
-        return
-    try:
-        fn = ctypes.CDLL(path).gsx_torch_compiled_ops
-    except (OSError, AttributeError):
-        return
-    fn.restype = ctypes.c_char_p
-    COMPILED_OPS = frozenset(fn().decode().split())
-    global _COMPILED_ISECT, _set_hint_compiled
-    try:
-        _set_hint_compiled = ctypes.CDLL(path).gsx_torch_set_long_tile_hint
-        _set_hint_compiled.argtypes, _set_hint_compiled.restype = [ctypes.c_int64], None
-    except (OSError, AttributeError):
-        _set_hint_compiled = None
-    _COMPILED_ISECT = (hasattr(torch.ops, "gsplat_amd") and hasattr(torch.ops.gsplat_amd, "isect_fused_begin")
-                       and os.environ.get("GSPLAT_AMD_COMPILED_OPS", "1") not in ("0", "")
-                       and os.environ.get("GSPLAT_AMD_COMPILED_ISECT", "1") not in ("0", ""))  # A/B switch
-
-
-COMPOSITE_UNAVAILABLE = _load_torch_classes()
 
 SCHEMAS = {
     # gsplat/cuda/ext.cpp:984-991
@@ -618,69 +541,10 @@ def _scan_i32(x: Tensor) -> Tensor:
     return out
 
 
-def _isect_fused_count(st, tile_mask):
-    """Count half of the fused intersection through the C-ABI: the tile-owner-major path (csrc/isect_binned.hip) when
-    st.binned, else the Gaussian-major one (csrc/isect_fused.hip). The grand total is written by the last kernel straight
-    into the pinned host word st.host_total (no copy kernel)."""
-    means2d, radii, depths, conics, opacities, _ = st.args
-    tile_size, tile_width, tile_height = st.geom[:3]
-    dev = means2d.device
-    tpg = None if st.tiles_per_gauss is None else ptr(st.tiles_per_gauss)
-    if st.binned:
-        st.count_ws = torch.empty(_cabi.isect_binned_count_workspace_bytes(st.rows, st.I, tile_width, tile_height), device=dev,
-                                  dtype=torch.uint8)
-        call("gsx_isect_binned_count", ptr(means2d), ptr(radii), ptr(depths), ptr(conics), ptr(opacities), ptr(tile_mask),
-             st.rows, st.I, tile_size, tile_width, tile_height, tpg, ptr(st.offsets), _cabi.ptr_host(st.host_total),
-             _cabi.ptr_host(st.host_total) + 8, ptr(st.count_ws), st.count_ws.numel())
-    else:
-        st.count_ws = torch.empty(_cabi.isect_fused_count_workspace_bytes(st.rows, st.I, tile_width, tile_height), device=dev,
-                                  dtype=torch.uint8)
-        call("gsx_isect_fused_count", ptr(means2d), ptr(radii), ptr(conics), ptr(opacities), ptr(tile_mask), st.rows, st.I,
-             tile_size, tile_width, tile_height, tpg, ptr(st.offsets), _cabi.ptr_host(st.host_total),
-             _cabi.ptr_host(st.host_total) + 8, ptr(st.count_ws), st.count_ws.numel())
-
-
-def _isect_fused_emit(st, tile_mask, n_isects):
-    """Emit + sort half (after the host read n_isects); returns (isect_ids, flatten_ids)."""
-    means2d, radii, depths, conics, opacities, _ = st.args
-    tile_size, tile_width, tile_height = st.geom[:3]
-    dev = means2d.device
-    isect_ids = torch.empty(n_isects, device=dev, dtype=torch.int64)
-    flatten_ids = torch.empty(n_isects, device=dev, dtype=torch.int32)
-    if n_isects == 0:
-        return isect_ids, flatten_ids
-    if st.binned:
-        ws = torch.empty(_cabi.isect_binned_emit_workspace_bytes(n_isects), device=dev, dtype=torch.uint8)
-        call("gsx_isect_binned_emit_sort", st.rows, st.I, tile_size, tile_width, tile_height, ptr(st.count_ws),
-             st.count_ws.numel(), ptr(st.offsets), n_isects, int(isect_max_tile_len(st)), ptr(isect_ids), ptr(flatten_ids),
-             ptr(ws), ws.numel())
-    else:
-        ws = torch.empty(_cabi.isect_fused_emit_workspace_bytes(n_isects, st.I, tile_width, tile_height), device=dev,
-                         dtype=torch.uint8)
-        call("gsx_isect_fused_emit_sort", ptr(means2d), ptr(radii), ptr(depths), ptr(conics), ptr(opacities), ptr(tile_mask),
-             st.rows, st.I, tile_size, tile_width, tile_height, ptr(st.count_ws), st.count_ws.numel(), ptr(st.offsets),
-             n_isects, ptr(isect_ids), ptr(flatten_ids), ptr(ws), ws.numel())
-    return isect_ids, flatten_ids
-
-
-def _isect_fused_total(st, tile_mask):
-    """Host sync on the count; reruns the Gaussian-major count when the binned path reports GSX_ISECT_RETRY (-2)."""
-    n_isects = int(st.host_total[0].item())
-    if st.binned and n_isects == -2:
-        st.binned = False
-        _cabi._lib.gsx_isect_binned_note_retry(st.rows, st.I, st.geom[1], st.geom[2])  # not tried again for the next 63 calls
-        _isect_fused_count(st, tile_mask)
-        torch.cuda.current_stream(st.args[0].device).synchronize()
-        n_isects = int(st.host_total[0].item())
-    if n_isects >= 2**31:
-        raise RuntimeError(f"intersect_tile: {n_isects} intersections overflow the int32 index space")
-    return n_isects
-
-
 class _IsectPending:
     """State between the two halves of intersect_tile (see isect_begin)."""
     __slots__ = ("args", "tiles_per_gauss", "cum", "host_total", "event", "rows", "n_per", "I", "geom", "sort",
-                 "fused", "binned", "count_ws", "offsets", "n_dev")
+                 "fused", "count_ws", "offsets")
 
 
 def isect_begin(means2d, radii, depths, conics, opacities, image_ids, gaussian_ids, n_images, tile_size,
@@ -730,28 +594,19 @@ def isect_begin(means2d, radii, depths, conics, opacities, image_ids, gaussian_i
     st.rows, st.n_per, st.I, st.sort = rows, n_per, I, sort
     st.geom = (tile_size, tile_width, tile_height, tile_bits, image_bits)
     st.tiles_per_gauss = torch.empty(out_shape, device=dev, dtype=torch.int32)
-    st.cum = st.host_total = st.event = st.count_ws = st.offsets = st.n_dev = None
-    st.fused = st.binned = False
+    st.cum = st.host_total = st.event = st.count_ws = st.offsets = None
+    st.fused = False
     if rows == 0:
         return st
-    # sort=True: fused path (csrc/isect_fused.hip) — per-(chunk, tile) histogram while counting, emission straight into
-    # tile segments, offsets as a by-product; dense rows of any image count, packed rows of a single image
+    # sort=True: fused path (csrc/isect_fused.hip, csrc/isect_binned.hip) — per-(chunk, tile) histogram while counting,
+    # emission straight into tile segments, offsets as a by-product; dense rows of any image count, packed rows of a single
+    # image. Its compiled halves (csrc/torch_ops.cpp) bring the count back through a polled pinned word, not an event.
     st.fused = bool(sort) and not f64 and _cabi.isect_fused_supported(I, tile_width, tile_height, packed)
-    if st.fused and _COMPILED_ISECT:
-        # compiled halves (csrc/torch_ops.cpp): same launches, ~30 us less interpreter time per step, and the count comes
-        # back through a polled pinned word instead of an event
+    if st.fused:
         st.tiles_per_gauss, st.offsets, st.count_ws, st.host_total = torch.ops.gsplat_amd.isect_fused_begin(
             means2d, radii, depths, conics, opacities, rows, I, tile_size, tile_width, tile_height, list(out_shape))
-        st.event = "polled"
         return st
-    st.host_total = torch.zeros(2, dtype=torch.int64, pin_memory=True)  # [n_isects, longest tile list]
-    if st.fused:
-        st.offsets = torch.empty(I * tile_width * tile_height, device=dev, dtype=torch.int32)
-        st.binned = _cabi.isect_binned_should_try(rows, I, tile_width, tile_height, packed)  # once; st carries it
-        _isect_fused_count(st, None)
-        st.event = torch.cuda.Event()
-        st.event.record()
-        return st
+    st.host_total = torch.zeros(1, dtype=torch.int64, pin_memory=True)  # n_isects
     if f64:
         call("gsx_isect_count_f64", ptr(means2d), ptr(radii), ptr(image_ids), rows, n_per, I, tile_size, tile_width,
              tile_height, ptr(st.tiles_per_gauss))
@@ -767,9 +622,7 @@ def isect_begin(means2d, radii, depths, conics, opacities, image_ids, gaussian_i
 
 def isect_max_tile_len(st: "_IsectPending") -> int:
     """Length of the longest tile list (0 when the path taken does not report it). Valid after isect_finish()."""
-    if st.host_total is None or st.host_total.numel() < 2 or not st.fused:
-        return 0
-    return int(st.host_total[1].item())
+    return int(st.host_total[1].item()) if st.fused else 0
 
 
 def isect_finish(st: "_IsectPending"):
@@ -782,17 +635,12 @@ def isect_finish(st: "_IsectPending"):
     if rows == 0:
         return (tiles_per_gauss, torch.empty(0, device=dev, dtype=torch.int64),
                 torch.empty(0, device=dev, dtype=torch.int32))
-    if st.event == "polled":  # compiled second half: waits for the count (the one host round trip), allocates, emits, sorts
+    if st.fused:  # compiled second half: waits for the count (the one host round trip), allocates, emits, sorts, notes
         isect_ids, flatten_ids = torch.ops.gsplat_amd.isect_fused_finish(
             means2d, radii, depths, conics, opacities, rows, I, tile_size, tile_width, tile_height, st.count_ws, st.offsets,
             st.host_total, tiles_per_gauss)
         return tiles_per_gauss, isect_ids, flatten_ids
     st.event.synchronize()  # host sync: exact-length outputs (reference: Intersect.cpp:258-259)
-    if st.fused:
-        n_isects = _isect_fused_total(st, None)
-        isect_ids, flatten_ids = _isect_fused_emit(st, None, n_isects)
-        _note_longest(flatten_ids, isect_max_tile_len(st))
-        return tiles_per_gauss, isect_ids, flatten_ids
     n_isects = int(st.host_total[0].item())
     cum = st.cum
     if n_isects >= 2**31:
@@ -919,14 +767,6 @@ def intersect_tile_lidar(lidar, means2d, radii, depths, image_ids, gaussian_ids,
     return tiles_per_gauss, isect_ids, flatten_ids
 
 
-@_op("intersect_offset")
-def intersect_offset(isect_ids, I, tile_width, tile_height):
-    isect_ids = isect_ids.contiguous()
-    offsets = torch.empty((I, tile_height, tile_width), device=isect_ids.device, dtype=torch.int32)
-    call("gsx_isect_offsets", ptr(isect_ids), isect_ids.numel(), I, tile_width, tile_height, ptr(offsets))
-    return offsets
-
-
 # ----------------------------------------------------------------------------------------------
 # projection
 # ----------------------------------------------------------------------------------------------
@@ -952,34 +792,6 @@ def _f64_instantiation(fn):
         return tuple(up(t) for t in out)
 
     return body
-
-
-def _check_proj_inputs(means, covars, quats, scales, viewmats, Ks):
-    _check_f32(means=means, covars=covars, quats=quats, scales=scales, viewmats=viewmats, Ks=Ks)
-    if covars is None and (quats is None or scales is None):
-        raise ValueError("projection: either covars or (quats, scales) must be given")
-
-
-@_op("projection_ewa_3dgs_fused")
-@_f64_instantiation
-def projection_ewa_3dgs_fused(means, covars, quats, scales, opacities, viewmats, Ks, image_width, image_height,
-                              eps2d, near_plane, far_plane, radius_clip, calc_compensations, camera_model):
-    _check_proj_inputs(means, covars, quats, scales, viewmats, Ks)
-    batch_dims, B, C, N = _proj_dims(means, viewmats)
-    means, viewmats, Ks = means.contiguous(), viewmats.contiguous(), Ks.contiguous()
-    covars, quats, scales, opacities = _c(covars), _c(quats), _c(scales), _c(opacities)
-    dev, dt = means.device, means.dtype
-    shape = tuple(batch_dims) + (C, N)
-    radii = torch.empty(shape + (2,), device=dev, dtype=torch.int32)
-    means2d = torch.empty(shape + (2,), device=dev, dtype=dt)
-    depths = torch.empty(shape, device=dev, dtype=dt)
-    conics = torch.empty(shape + (3,), device=dev, dtype=dt)
-    comps = torch.empty(shape, device=dev, dtype=dt) if calc_compensations else None
-    call("gsx_project_ewa_fwd", ptr(means), ptr(covars), ptr(None if covars is not None else quats),
-         ptr(None if covars is not None else scales), ptr(opacities), ptr(viewmats), ptr(Ks), B, C, N, image_width,
-         image_height, eps2d, near_plane, far_plane, radius_clip, int(camera_model), ptr(radii), ptr(means2d),
-         ptr(depths), ptr(conics), ptr(comps))
-    return radii, means2d, depths, conics, comps
 
 
 @_op("projection_ewa_3dgs_fused_bwd")
@@ -1014,66 +826,6 @@ def projection_ewa_3dgs_fused_bwd(means, covars, quats, scales, viewmats, Ks, im
         return v_means, v_covars, v_quats, v_scales, v_viewmats, v_opacities
     call("gsx_project_ewa_bwd", *head, ptr(v_means), ptr(v_covars), ptr(v_quats), ptr(v_scales), ptr(v_viewmats))
     return v_means, v_covars, v_quats, v_scales, v_viewmats
-
-
-_PACKED_ROW_BYTES = 64  # 3 int64 ids + radii + means2d + depth + conic (+ compensation) per packed row
-_PACKED_PREALLOC_LIMIT = 1 << 30  # upper-bound row buffers are only used below this size
-_PACKED_COMPACT_ABOVE = 1 << 28  # ... and their unused tails are given back when they exceed this many bytes
-
-
-@_op("projection_ewa_3dgs_packed")
-@_f64_instantiation
-def projection_ewa_3dgs_packed(means, covars, quats, scales, opacities, viewmats, Ks, image_width, image_height,
-                               eps2d, near_plane, far_plane, radius_clip, sparse_grad, calc_compensations,
-                               camera_model):
-    _check_proj_inputs(means, covars, quats, scales, viewmats, Ks)
-    batch_dims, B, C, N = _proj_dims(means, viewmats)
-    means, viewmats, Ks = means.contiguous(), viewmats.contiguous(), Ks.contiguous()
-    covars, quats, scales, opacities = _c(covars), _c(quats), _c(scales), _c(opacities)
-    dev, dt = means.device, means.dtype
-    q = None if covars is not None else quats
-    s = None if covars is not None else scales
-    total = B * C * N
-    common = (ptr(means), ptr(covars), ptr(q), ptr(s), ptr(opacities), ptr(viewmats), ptr(Ks), B, C, N, image_width,
-              image_height, eps2d, near_plane, far_plane, radius_clip, int(camera_model))
-
-    def outputs(rows):
-        return (torch.empty(rows, device=dev, dtype=torch.int64), torch.empty(rows, device=dev, dtype=torch.int64),
-                torch.empty(rows, device=dev, dtype=torch.int64), torch.zeros(B * C + 1, device=dev, dtype=torch.int32),
-                torch.empty((rows, 2), device=dev, dtype=torch.int32), torch.empty((rows, 2), device=dev, dtype=dt),
-                torch.empty((rows,), device=dev, dtype=dt), torch.empty((rows, 3), device=dev, dtype=dt),
-                torch.empty((rows,), device=dev, dtype=dt) if calc_compensations else None)
-
-    if total == 0:
-        return outputs(0)
-    # Rows are placed from BLOCK counts (csrc/projection.hip: PackedBlocks): one int32 per 256 (image, Gaussian) pairs, scanned
-    # by one workgroup that stores the row count straight into a pinned host word - no per-pair flags, no cumsum tensor.
-    n_blocks = _cabi._lib.gsx_project_packed_blocks(total)
-    blocks = torch.empty((2, n_blocks), device=dev, dtype=torch.int32)
-    host_nnz = torch.full((1,), -1, dtype=torch.int64).pin_memory()
-    call("gsx_project_ewa_packed_count_blocks", *common, int(calc_compensations), ptr(blocks[0]), ptr(blocks[1]), None,
-         host_nnz.data_ptr())
-    ev = torch.cuda.Event()
-    ev.record()
-    prealloc = total * _PACKED_ROW_BYTES <= _PACKED_PREALLOC_LIMIT
-    if prealloc:
-        # The write pass only needs the DEVICE-side offsets: enqueue it into row buffers sized for the upper bound (every
-        # pair visible) before the host learns nnz, and hand out the first nnz rows. Scenes whose upper bound would not be
-        # small next to the model keep the exact-length path below - saving that memory is what packed rows are for.
-        bufs = outputs(total)
-        call("gsx_project_ewa_packed_write_blocks", *common, ptr(blocks[1]), *[ptr(t) for t in bufs])
-    ev.synchronize()  # host round trip: exact-length COO outputs (reference: Projection.cpp:928-941)
-    nnz = int(host_nnz.item())
-    if prealloc:
-        # a view pins the whole upper-bound buffer for as long as the step (and its autograd graph) holds the rows: copy the
-        # heads out and let the big buffers go only when that is a real amount of memory - seven copies cost 32 us of kernels
-        # and as much host time, which left the GPU idle behind the write pass (c3 at 25 % visibility: packed 0.86 ms per
-        # step against dense 0.80, profiles/r08_ab.md #28)
-        compact = (total - nnz) * _PACKED_ROW_BYTES > _PACKED_COMPACT_ABOVE
-        return tuple(t if (t is None or i == 3) else (t[:nnz].clone() if compact else t[:nnz]) for i, t in enumerate(bufs))
-    bufs = outputs(nnz)
-    call("gsx_project_ewa_packed_write_blocks", *common, ptr(blocks[1]), *[ptr(t) for t in bufs])
-    return bufs
 
 
 @_op("projection_ewa_3dgs_packed_bwd")
@@ -1168,43 +920,6 @@ def projection_ewa_3dgs_packed_bwd(means, covars, quats, scales, viewmats, Ks, i
 def _raster_dims(isect_offsets, colors):
     image_dims = tuple(isect_offsets.shape[:-2])
     return image_dims, math.prod(image_dims), isect_offsets.shape[-2], isect_offsets.shape[-1], colors.shape[-1]
-
-
-@_op("rasterize_to_pixels_3dgs")
-def rasterize_to_pixels_3dgs(means2d, conics, colors, opacities, backgrounds, masks, image_width, image_height,
-                             tile_size, isect_offsets, flatten_ids, packed, absgrad):
-    _check_f32(means2d=means2d, conics=conics, colors=colors, opacities=opacities, backgrounds=backgrounds)
-    as_received = (means2d, conics, colors, opacities, isect_offsets, flatten_ids)  # key of the segment-workspace note
-    image_dims, I, th, tw, D = _raster_dims(isect_offsets, colors)
-    if th * tile_size < image_height or tw * tile_size < image_width:
-        raise ValueError("rasterize_to_pixels: isect_offsets tile grid does not cover the image")
-    if masks is not None and masks.dtype != torch.bool:
-        raise TypeError("masks must be a bool tensor")
-    means2d, conics, colors, opacities = (means2d.contiguous(), conics.contiguous(), colors.contiguous(),
-                                          opacities.contiguous())
-    backgrounds, masks = _c(backgrounds), _c(masks)
-    isect_offsets, flatten_ids = isect_offsets.contiguous(), flatten_ids.contiguous()
-    dev, dt = means2d.device, means2d.dtype
-    renders = torch.empty(image_dims + (image_height, image_width, D), device=dev, dtype=dt)
-    alphas = torch.empty(image_dims + (image_height, image_width, 1), device=dev, dtype=dt)
-    last_ids = torch.empty(image_dims + (image_height, image_width), device=dev, dtype=torch.int32)
-    longest = _consume_long_tile_hint() or _lookup_longest(flatten_ids)
-    if longest > SEG_MIN_LONGEST and longest > _seg_cut(flatten_ids.numel(), I, tw, th):
-        ws = torch.empty(_cabi._lib.gsx_raster3d_seg_workspace_bytes(flatten_ids.numel(), I, tw, th, D, SEG_LEN), device=dev,
-                         dtype=torch.uint8)
-        call("gsx_raster3d_fwd_seg", ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds), ptr(masks),
-             ptr(isect_offsets), ptr(flatten_ids), I, flatten_ids.numel(), D, image_width, image_height, tile_size, tw,
-             th, ptr(renders), ptr(alphas), ptr(last_ids), SEG_LEN, ptr(ws), ws.numel())
-        if D <= 4 and tile_size == 16:
-            # the backward over these lists starts its slices from the sums this call left in `ws` (no pre-pass): noted
-            # under the identity of last_ids, the tensor every autograd formula hands to the backward op
-            _note_seg_workspace(last_ids, ws, flatten_ids.numel(), D, as_received)
-    else:
-        call("gsx_raster3d_fwd", ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds), ptr(masks),
-             ptr(isect_offsets), ptr(flatten_ids), I, flatten_ids.numel(), D, image_width, image_height, tile_size, tw,
-             th, ptr(renders), ptr(alphas), ptr(last_ids))
-    holder = torch.zeros_like(means2d) if absgrad else torch.empty(0, device=dev, dtype=dt)
-    return renders, alphas, holder, last_ids
 
 
 def _pixel_linear_strides(t):
@@ -1508,25 +1223,6 @@ def _check_2dgs_inputs(means, quats, scales, viewmats, Ks):
                          f"scales {tuple(scales.shape)}")
 
 
-@_op("projection_2dgs_fused")
-def projection_2dgs_fused(means, quats, scales, viewmats, Ks, image_width, image_height, eps2d, near_plane, far_plane,
-                          radius_clip):
-    _check_2dgs_inputs(means, quats, scales, viewmats, Ks)
-    batch_dims, B, C, N = _proj_dims(means, viewmats)
-    means, quats, scales, viewmats, Ks = (t.contiguous() for t in (means, quats, scales, viewmats, Ks))
-    dev, dt = means.device, means.dtype
-    shape = tuple(batch_dims) + (C, N)
-    radii = torch.empty(shape + (2,), device=dev, dtype=torch.int32)
-    means2d = torch.empty(shape + (2,), device=dev, dtype=dt)
-    depths = torch.empty(shape, device=dev, dtype=dt)
-    ray_transforms = torch.empty(shape + (3, 3), device=dev, dtype=dt)
-    normals = torch.empty(shape + (3,), device=dev, dtype=dt)
-    call("gsx_project_2dgs_fwd", ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), B, C, N, image_width,
-         image_height, near_plane, far_plane, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(ray_transforms),
-         ptr(normals))
-    return radii, means2d, depths, ray_transforms, normals
-
-
 @_op("projection_2dgs_fused_bwd")
 def projection_2dgs_fused_bwd(means, quats, scales, viewmats, Ks, image_width, image_height, radii, ray_transforms,
                               v_means2d, v_depths, v_ray_transforms, v_normals, viewmats_requires_grad, *,
@@ -1616,37 +1312,6 @@ def projection_2dgs_packed_bwd(means, quats, scales, viewmats, Ks, image_width, 
     call("gsx_project_2dgs_packed_bwd", *head, ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_viewmats))
     clear_row_map_cache()
     return v_means, v_quats, v_scales, v_viewmats
-
-
-@_op("rasterize_to_pixels_2dgs")
-def rasterize_to_pixels_2dgs(means2d, ray_transforms, colors, opacities, normals, densify, backgrounds, masks,
-                             image_width, image_height, tile_size, tile_offsets, flatten_ids, packed, absgrad, distloss):
-    _check_f32(means2d=means2d, ray_transforms=ray_transforms, colors=colors, opacities=opacities, normals=normals,
-               backgrounds=backgrounds)
-    image_dims, I, th, tw, D = _raster_dims(tile_offsets, colors)
-    if th * tile_size < image_height or tw * tile_size < image_width:
-        raise ValueError("rasterize_to_pixels_2dgs: tile grid does not cover the image")
-    if masks is not None and masks.dtype != torch.bool:
-        raise TypeError("masks must be a bool tensor")
-    means2d, ray_transforms, colors, opacities, normals = (t.contiguous() for t in (means2d, ray_transforms, colors,
-                                                                                    opacities, normals))
-    backgrounds, masks = _c(backgrounds), _c(masks)
-    tile_offsets, flatten_ids = tile_offsets.contiguous(), flatten_ids.contiguous()
-    dev, dt = means2d.device, means2d.dtype
-    hw = image_dims + (image_height, image_width)
-    renders = torch.empty(hw + (D,), device=dev, dtype=dt)
-    alphas = torch.empty(hw + (1,), device=dev, dtype=dt)
-    rnormals = torch.empty(hw + (3,), device=dev, dtype=dt)
-    rdistort = torch.empty(hw + (1,), device=dev, dtype=dt)
-    rmedian = torch.empty(hw + (1,), device=dev, dtype=dt)
-    last_ids = torch.empty(hw, device=dev, dtype=torch.int32)
-    median_ids = torch.empty(hw, device=dev, dtype=torch.int32)
-    call("gsx_raster2d_fwd", ptr(means2d), ptr(ray_transforms), ptr(colors), ptr(opacities), ptr(normals),
-         ptr(backgrounds), ptr(masks), ptr(tile_offsets), ptr(flatten_ids), I, flatten_ids.numel(), D, image_width,
-         image_height, tile_size, tw, th, int(distloss), ptr(renders), ptr(alphas), ptr(rnormals), ptr(rdistort),
-         ptr(rmedian), ptr(last_ids), ptr(median_ids))
-    holder = torch.zeros_like(means2d) if absgrad else torch.empty(0, device=dev, dtype=dt)
-    return renders, alphas, rnormals, rdistort, rmedian, holder, last_ids, median_ids
 
 
 @_op("rasterize_to_pixels_2dgs_bwd")
@@ -1811,20 +1476,46 @@ def intersect_tile_sparse(means2d, radii, depths, image_ids, tile_mask, active_t
         # the dense fused path with the tile mask applied inside the walk (AABB test: conics / opacities NULL, as the
         # reference's sparse enumeration, Intersect.cpp:617-634): inactive tiles get empty segments, so the dense
         # offsets of the active tiles ARE the compacted offsets
-        st = _IsectPending()
-        st.args = (means2d, radii, depths, None, None, None)
-        st.rows, st.I, st.geom = rows, I, (tile_size, tile_width, tile_height)
-        st.tiles_per_gauss = st.cum = st.event = st.count_ws = st.n_dev = None
-        st.n_per, st.sort, st.fused = 1, True, True  # every slot set: _isect_fused_emit reads st.fused through isect_max_tile_len
-        st.offsets = offsets = torch.empty(I * n_tiles, device=dev, dtype=torch.int32)
-        st.host_total = torch.zeros(2, dtype=torch.int64, pin_memory=True)
-        st.binned = _cabi.isect_binned_should_try(rows, I, tile_width, tile_height, packed)  # once; st carries it
-        _isect_fused_count(st, tile_mask)
-        torch.cuda.current_stream(dev).synchronize()  # host sync: exact-length outputs (reference: Intersect.cpp:637)
-        n_isects = _isect_fused_total(st, tile_mask)
+        offsets = torch.empty(I * n_tiles, device=dev, dtype=torch.int32)
+        host_total = torch.zeros(2, dtype=torch.int64, pin_memory=True)  # [n_isects, longest tile list]
+        geom = (rows, I, tile_size, tile_width, tile_height)
+        hosts = (_cabi.ptr_host(host_total), _cabi.ptr_host(host_total) + 8)
+
+        def count(binned):  # the tile-owner-major count (csrc/isect_binned.hip) or the Gaussian-major one (isect_fused.hip)
+            if binned:
+                ws = torch.empty(_cabi.isect_binned_count_workspace_bytes(rows, I, tile_width, tile_height), device=dev,
+                                 dtype=torch.uint8)
+                call("gsx_isect_binned_count", ptr(means2d), ptr(radii), ptr(depths), None, None, ptr(tile_mask), *geom, None,
+                     ptr(offsets), *hosts, ptr(ws), ws.numel())
+            else:
+                ws = torch.empty(_cabi.isect_fused_count_workspace_bytes(rows, I, tile_width, tile_height), device=dev,
+                                 dtype=torch.uint8)
+                call("gsx_isect_fused_count", ptr(means2d), ptr(radii), None, None, ptr(tile_mask), *geom, None, ptr(offsets),
+                     *hosts, ptr(ws), ws.numel())
+            torch.cuda.current_stream(dev).synchronize()  # host sync: exact-length outputs (reference: Intersect.cpp:637)
+            return ws, int(host_total[0].item())
+
+        binned = _cabi.isect_binned_should_try(rows, I, tile_width, tile_height, packed)  # once: the emit follows the count
+        count_ws, n_isects = count(binned)
+        if binned and n_isects == -2:  # GSX_ISECT_RETRY: count again Gaussian-major, not tried again for the next 63 calls
+            binned = False
+            _cabi._lib.gsx_isect_binned_note_retry(rows, I, tile_width, tile_height)
+            count_ws, n_isects = count(False)
+        if n_isects >= 2**31:
+            raise RuntimeError(f"intersect_tile: {n_isects} intersections overflow the int32 index space")
         if n_isects == 0:
             return empty
-        isect_ids, flatten_ids = _isect_fused_emit(st, tile_mask, n_isects)
+        isect_ids = torch.empty(n_isects, device=dev, dtype=torch.int64)
+        flatten_ids = torch.empty(n_isects, device=dev, dtype=torch.int32)
+        if binned:
+            ws = torch.empty(_cabi.isect_binned_emit_workspace_bytes(n_isects), device=dev, dtype=torch.uint8)
+            call("gsx_isect_binned_emit_sort", *geom, ptr(count_ws), count_ws.numel(), ptr(offsets), n_isects,
+                 int(host_total[1].item()), ptr(isect_ids), ptr(flatten_ids), ptr(ws), ws.numel())
+        else:
+            ws = torch.empty(_cabi.isect_fused_emit_workspace_bytes(n_isects, I, tile_width, tile_height), device=dev,
+                             dtype=torch.uint8)
+            call("gsx_isect_fused_emit_sort", ptr(means2d), ptr(radii), ptr(depths), None, None, ptr(tile_mask), *geom,
+                 ptr(count_ws), count_ws.numel(), ptr(offsets), n_isects, ptr(isect_ids), ptr(flatten_ids), ptr(ws), ws.numel())
         return torch.cat([offsets[active_tiles.long()], sentinel(n_isects)]), flatten_ids
     # packed rows of several images / tile grids beyond the fused path's LDS histogram: enumerate every tile with the
     # generic kernels, then drop the intersections of inactive tiles (order within a tile is preserved)
@@ -1836,7 +1527,7 @@ def intersect_tile_sparse(means2d, radii, depths, image_ids, tile_mask, active_t
     key_hi = isect_ids >> 32
     keep = tile_mask.reshape(-1)[(key_hi >> tile_bits) * n_tiles + (key_hi & ((1 << tile_bits) - 1))]
     isect_ids, flatten_ids = isect_ids[keep], flatten_ids[keep]
-    offsets = intersect_offset(isect_ids, I, tile_width, tile_height).reshape(-1)
+    offsets = torch.ops.gsplat.intersect_offset(isect_ids, I, tile_width, tile_height).reshape(-1)
     return torch.cat([offsets[active_tiles.long()], sentinel(flatten_ids.shape[0])]), flatten_ids
 
 
@@ -2818,12 +2509,6 @@ def rasterization_2dgs(means, quats, scales, opacities, colors, viewmats, Ks, im
 # ----------------------------------------------------------------------------------------------
 # registration
 # ----------------------------------------------------------------------------------------------
-def _os_environ_get(k, d):
-    import os
-
-    return os.environ.get(k, d)
-
-
 class CheckError(RuntimeError, ValueError):
     """A failed argument check of an op body, as the DISPATCHER reports it. The reference's bodies use TORCH_CHECK, which
     Python sees as RuntimeError (its tests assert `pytest.raises(RuntimeError, match=...)`); this package's own Python API
@@ -2859,32 +2544,28 @@ def _register():
         qual = f"{NS}::{name}"
         try:
             torch._C._dispatch_find_schema_or_throw(qual, "")
-            exists = True
         except RuntimeError:
-            exists = False
-        if not exists:
             _lib_def.define(name + schema)
-        fn = _impls[name]
-        if name not in COMPILED_OPS:
-            _lib_impl.impl(name, fn)
-        elif _os_environ_get("GSPLAT_AMD_COMPILED_OPS", "1") in ("0", ""):
-            _lib_impl.impl(name, fn, allow_override=True)
-    if COMPOSITE_UNAVAILABLE is None:
-        for name, schema in COMPOSITE_SCHEMAS.items():
-            try:
-                torch._C._dispatch_find_schema_or_throw(f"{NS}::{name}", "")
-            except RuntimeError:
-                _lib_def.define(name + schema)
+        if name in _impls:
             _lib_impl.impl(name, _impls[name])
+        elif not torch._C._dispatch_has_kernel_for_dispatch_key(qual, "CUDA"):  # a compiled body (csrc/torch_ops.cpp)
+            raise ImportError(f"gsplat_amd: {qual} has no body; rebuild {_cabi.torch_lib_path()} "
+                              "(make -C gsplat_amd/csrc torch)")
+    for name, schema in COMPOSITE_SCHEMAS.items():
+        try:
+            torch._C._dispatch_find_schema_or_throw(f"{NS}::{name}", "")
+        except RuntimeError:
+            _lib_def.define(name + schema)
+        _lib_impl.impl(name, _impls[name])
+        _lib_impl_autograd.impl(name, _impls[name])
+    for name, schema in CLASS_SCHEMAS.items():
+        try:
+            torch._C._dispatch_find_schema_or_throw(f"{NS}::{name}", "")
+        except RuntimeError:
+            _lib_def.define(name + schema)
+        _lib_impl.impl(name, _impls[name])
+        if name in _SELF_DIFFERENTIABLE:  # the body builds its own autograd graph (torch.autograd.Function inside)
             _lib_impl_autograd.impl(name, _impls[name])
-        for name, schema in CLASS_SCHEMAS.items():
-            try:
-                torch._C._dispatch_find_schema_or_throw(f"{NS}::{name}", "")
-            except RuntimeError:
-                _lib_def.define(name + schema)
-            _lib_impl.impl(name, _impls[name])
-            if name in _SELF_DIFFERENTIABLE:  # the body builds its own autograd graph (torch.autograd.Function inside)
-                _lib_impl_autograd.impl(name, _impls[name])
 
 
 _register()
@@ -2896,5 +2577,12 @@ def op(name: str):
 
 
 def impl(name: str):
-    """The Python implementation behind the op (lets internal callers pass private keyword options)."""
-    return _impls[name]
+    """The body behind the op: its Python function (lets internal callers pass private keyword options), or for an op whose
+    body is compiled the dispatcher entry."""
+    return _impls[name] if name in _impls else op(name)
+
+
+# an op whose body is compiled is reachable under its name here too, like every op with a Python body
+for _name in SCHEMAS:
+    if _name not in _impls:
+        globals()[_name] = op(_name)

@@ -1,15 +1,17 @@
-// Compiled op bodies: TORCH_LIBRARY_IMPL(gsplat, CUDA, ...) for the hot stage ops, calling the C-ABI of libgsplat_amd.so
-// (INTEGRATION.md route B). Host C++ only - no device code here; the kernels stay behind include/gsplat_amd.h.
+// Compiled op bodies: TORCH_LIBRARY_IMPL(gsplat, CUDA, ...) for the forward stage ops on the critical host path of
+// rasterization() / rasterization_2dgs(), calling the C-ABI of libgsplat_amd.so (INTEGRATION.md route B). Host C++ only - no
+// device code here; the kernels stay behind include/gsplat_amd.h.
 //
 // What an op body does is what the reference's host functions do around their kernels (shape checks, output allocation
 // from the inputs' options, current stream, device guard, error translation):
-//   projection_ewa_3dgs_fused{,_bwd}   gsplat/cuda/csrc/Projection.cpp:366-440, 579-694
-//   spherical_harmonics{,_bwd}         gsplat/cuda/csrc/SphericalHarmonics.cpp (ext.cpp:994-1014)
-//   intersect_tile, intersect_offset   gsplat/cuda/csrc/Intersect.cpp:170-329
-//   rasterize_to_pixels_3dgs{,_bwd}    gsplat/cuda/csrc/Rasterization.cpp:275-365, 484-587
-// The Python bodies in gsplat_amd/_ops.py remain the implementation of every other op and of the private fast paths of
-// gsplat_amd/rendering.py; _ops.py skips registering its own body for an op listed by gsx_torch_compiled_ops().
-// Schemas are defined by _ops.py (verbatim from ext.cpp); an IMPL block may be loaded before or after the definitions.
+//   projection_ewa_3dgs_fused / _packed      gsplat/cuda/csrc/Projection.cpp:366-440, 928-941
+//   intersect_offset                         gsplat/cuda/csrc/Intersect.cpp (isect_offset_encode)
+//   rasterize_to_pixels_3dgs                 gsplat/cuda/csrc/Rasterization.cpp:275-365
+//   projection_2dgs_fused, rasterize_to_pixels_2dgs (ext.cpp:1163-1199)
+// plus the two halves of the fused tile intersection (gsplat_amd::isect_fused_{begin,finish}) and the notes that carry the
+// longest tile list and the segment workspace between calls. Every other op body, the backward ones included, is Python
+// (gsplat_amd/_ops.py); each op has exactly one body. Schemas are defined by _ops.py (verbatim from ext.cpp); an IMPL block
+// may be loaded before or after the definitions.
 #include <chrono>
 #include <cstdlib>
 #include <thread>
@@ -116,46 +118,11 @@ template <class T> const T *cp(const OptTensor &t) { return has(t) ? cp<T>(*t) :
 template <class T> T *mp(Tensor &t) { return t.defined() && t.numel() ? t.mutable_data_ptr<T>() : nullptr; }
 const float *fp(const Tensor &t) { return cp<float>(t); }
 const float *fp(const OptTensor &t) { return cp<float>(t); }
-
-// (tensor, row stride in floats) of a [..., width] float tensor whose rows are `width` contiguous floats at a uniform stride -
-// e.g. a column view of the array-of-structures gradient rows returned by rasterize_to_pixels_3dgs_bwd - else a copy
-std::pair<Tensor, uint32_t> row_view(const Tensor &t, int64_t width)
-{
-    if (t.is_contiguous()) return {t, (uint32_t)width};
-    if (t.dim() >= 2 && t.size(-1) == width && t.stride(-1) == 1) {
-        const int64_t rs = t.stride(-2);
-        bool uniform = rs >= width;
-        int64_t expect = rs * t.size(-2);
-        for (int64_t d = t.dim() - 3; d >= 0 && uniform; --d) {
-            if (t.size(d) != 1 && t.stride(d) != expect) uniform = false;
-            expect *= t.size(d);
-        }
-        if (uniform) return {t, (uint32_t)rs};
-    }
-    return {t.contiguous(), (uint32_t)width};
-}
-std::pair<Tensor, uint32_t> row_view_1(const Tensor &t) // [...] scalars per row
-{
-    return {t.contiguous(), 1u};
-}
-
 int64_t prod(c10::IntArrayRef dims)
 {
     int64_t p = 1;
     for (auto d : dims) p *= d;
     return p;
-}
-
-uint32_t bits_for_count(int64_t count) // MathUtils.h:25-35
-{
-    uint32_t b = 0;
-    if (count <= 1) return 0;
-    uint64_t v = (uint64_t)count - 1;
-    while (v) {
-        ++b;
-        v >>= 1;
-    }
-    return b;
 }
 
 // ---- projection (dense) ------------------------------------------------------------------------------------------------
@@ -174,7 +141,6 @@ projection_ewa_3dgs_fused(const Tensor &means_, const OptTensor &covars_, const 
     want_f32(means_, "means"); want_f32(covars_, "covars"); want_f32(quats_, "quats"); want_f32(scales_, "scales");
     want_f32(viewmats_, "viewmats"); want_f32(Ks_, "Ks");
     TORCH_CHECK(has(covars_) || (has(quats_) && has(scales_)), "projection: either covars or (quats, scales) must be given");
-    Launch L(means_);
     const Tensor means = contig(means_), viewmats = contig(viewmats_), Ks = contig(Ks_);
     const OptTensor covars = contig(covars_), opac = contig(opacities_);
     const OptTensor quats = has(covars) ? OptTensor() : contig(quats_), scales = has(covars) ? OptTensor() : contig(scales_);
@@ -188,53 +154,14 @@ projection_ewa_3dgs_fused(const Tensor &means_, const OptTensor &covars_, const 
     Tensor conics = at::empty(with(3), means.options());
     OptTensor comps;
     if (calc_compensations) comps = at::empty(shape, means.options());
+    if (B * C * N == 0) return {radii, means2d, depths, conics, comps}; // nothing to launch (before the device is touched)
+    Launch L(means_);
     { Timed timed_("gsx_project_ewa_fwd", L.stream); check(gsx_project_ewa_fwd(fp(means), fp(covars), fp(quats), fp(scales), fp(opac), fp(viewmats), fp(Ks), (uint32_t)B,
                               (uint32_t)C, (uint32_t)N, (uint32_t)width, (uint32_t)height, (float)eps2d, (float)near_plane,
                               (float)far_plane, (float)radius_clip, (int)camera_model, mp<int32_t>(radii), mp<float>(means2d),
                               mp<float>(depths), mp<float>(conics), comps ? mp<float>(*comps) : nullptr, L.stream),
           "gsx_project_ewa_fwd"); }
     return {radii, means2d, depths, conics, comps};
-}
-
-std::tuple<Tensor, OptTensor, OptTensor, OptTensor, OptTensor>
-projection_ewa_3dgs_fused_bwd(const Tensor &means_, const OptTensor &covars_, const OptTensor &quats_, const OptTensor &scales_,
-                              const Tensor &viewmats_, const Tensor &Ks_, int64_t width, int64_t height, double eps2d,
-                              int64_t camera_model, const Tensor &radii, const Tensor &conics, const OptTensor &compensations,
-                              const Tensor &v_means2d_, const Tensor &v_depths_, const Tensor &v_conics_,
-                              const OptTensor &v_compensations, bool viewmats_requires_grad)
-{
-    if (is_f64(means_)) { // the double instantiation: double in memory, float arithmetic (see narrow32)
-        auto [vm, vc, vq, vs, vv] = projection_ewa_3dgs_fused_bwd(
-            narrow32(means_), narrow32(covars_), narrow32(quats_), narrow32(scales_), narrow32(viewmats_), narrow32(Ks_), width,
-            height, eps2d, camera_model, radii, narrow32(conics), narrow32(compensations), narrow32(v_means2d_),
-            narrow32(v_depths_), narrow32(v_conics_), narrow32(v_compensations), viewmats_requires_grad);
-        return {widen64(vm), widen64(vc), widen64(vq), widen64(vs), widen64(vv)};
-    }
-    Launch L(means_);
-    const Tensor means = contig(means_), viewmats = contig(viewmats_), Ks = contig(Ks_);
-    const OptTensor covars = contig(covars_);
-    const OptTensor quats = has(covars) ? OptTensor() : contig(quats_), scales = has(covars) ? OptTensor() : contig(scales_);
-    auto batch = means.sizes().slice(0, means.dim() - 2);
-    const int64_t B = prod(batch), C = viewmats.size(-3), N = means.size(-2);
-    Tensor v_means = at::empty_like(means);
-    OptTensor v_covars, v_quats, v_scales, v_viewmats;
-    if (has(covars)) v_covars = at::empty_like(*covars);
-    else { v_quats = at::empty_like(*quats); v_scales = at::empty_like(*scales); }
-    if (viewmats_requires_grad) v_viewmats = at::zeros_like(viewmats);
-    auto [vm2, m2s] = row_view(v_means2d_, 2);
-    auto [vcn, cns] = row_view(v_conics_, 3);
-    const Tensor vdep = v_depths_.defined() ? contig(v_depths_) : Tensor();
-    const Tensor rad = contig(radii), con = contig(conics);
-    const OptTensor comp = contig(compensations), vcomp = contig(v_compensations);
-    { Timed timed_("gsx_project_ewa_bwd", L.stream); check(gsx_project_ewa_bwd(fp(means), fp(covars), fp(quats), fp(scales), fp(viewmats), fp(Ks), (uint32_t)B, (uint32_t)C,
-                              (uint32_t)N, (uint32_t)width, (uint32_t)height, (float)eps2d, (int)camera_model,
-                              cp<int32_t>(rad), fp(con), fp(comp), vm2.const_data_ptr<float>(), m2s, fp(vdep),
-                              vcn.const_data_ptr<float>(), cns, fp(vcomp), mp<float>(v_means),
-                              v_covars ? mp<float>(*v_covars) : nullptr, v_quats ? mp<float>(*v_quats) : nullptr,
-                              v_scales ? mp<float>(*v_scales) : nullptr, v_viewmats ? mp<float>(*v_viewmats) : nullptr,
-                              L.stream),
-          "gsx_project_ewa_bwd"); }
-    return {v_means, v_covars, v_quats, v_scales, v_viewmats};
 }
 
 // ---- projection (packed rows) ----------------------------------------------------------------------------------------------
@@ -261,7 +188,6 @@ projection_ewa_3dgs_packed(const Tensor &means_, const OptTensor &covars_, const
     want_f32(means_, "means"); want_f32(covars_, "covars"); want_f32(quats_, "quats"); want_f32(scales_, "scales");
     want_f32(viewmats_, "viewmats"); want_f32(Ks_, "Ks");
     TORCH_CHECK(has(covars_) || (has(quats_) && has(scales_)), "projection: either covars or (quats, scales) must be given");
-    Launch L(means_);
     const Tensor means = contig(means_), viewmats = contig(viewmats_), Ks = contig(Ks_);
     const OptTensor covars = contig(covars_), opac = contig(opacities_);
     const OptTensor quats = has(covars) ? OptTensor() : contig(quats_), scales = has(covars) ? OptTensor() : contig(scales_);
@@ -273,7 +199,8 @@ projection_ewa_3dgs_packed(const Tensor &means_, const OptTensor &covars_, const
                                at::empty({rows, 2}, i32), at::empty({rows, 2}, f32), at::empty({rows}, f32),
                                at::empty({rows, 3}, f32), calc_compensations ? OptTensor(at::empty({rows}, f32)) : OptTensor());
     };
-    if (total == 0) return outputs(0);
+    if (total == 0) return outputs(0); // nothing to launch (before the device is touched)
+    Launch L(means_);
     auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(means.device().index());
     // rows are placed from BLOCK counts (csrc/projection.hip: PackedBlocks): one int32 per 256 pairs, scanned by one workgroup
     // that stores the row count straight into the pinned word below - no per-pair flags, no cumsum tensor, no copy kernel
@@ -331,225 +258,6 @@ projection_ewa_3dgs_packed(const Tensor &means_, const OptTensor &covars_, const
     if (nnz > 0 || true) write(nnz, o);
     return o;
 }
-
-// ---- spherical harmonics ------------------------------------------------------------------------------------------------
-struct ShDims {
-    bool packed;
-    int64_t B, C, N, K, D;
-};
-ShDims sh_dims(const Tensor &means, const Tensor &viewmats, const Tensor &coeffs, const OptTensor &gaussian_ids)
-{
-    ShDims d;
-    d.packed = has(gaussian_ids);
-    TORCH_CHECK(coeffs.dim() == 3, "coeffs must have shape [N, K, D] or [nnz, K, D], got ", coeffs.sizes());
-    d.B = prod(means.sizes().slice(0, means.dim() - 2));
-    d.C = viewmats.size(-3);
-    d.N = means.size(-2);
-    d.K = coeffs.size(-2);
-    d.D = coeffs.size(-1);
-    return d;
-}
-
-// The reference's input contract, message for message (SphericalHarmonics.cpp:38-131; Python twin: _ops._check_sh_inputs)
-void check_sh_inputs(int64_t degrees_to_use, const Tensor &means, const Tensor &viewmats, const Tensor &coeffs,
-                     const OptTensor &masks, const OptTensor &batch_ids, const OptTensor &camera_ids, const OptTensor &gaussian_ids)
-{
-    TORCH_CHECK(degrees_to_use >= 0 && degrees_to_use <= 4, "degrees_to_use must be between 0 and 4, got ", degrees_to_use);
-    TORCH_CHECK(means.dim() >= 2 && means.size(-1) == 3, "means must have shape [..., N, 3], got ", means.sizes());
-    TORCH_CHECK(viewmats.dim() == means.dim() + 1 && viewmats.size(-2) == 4 && viewmats.size(-1) == 4,
-                "viewmats must have shape [..., C, 4, 4], got ", viewmats.sizes());
-    TORCH_CHECK(means.sizes().slice(0, means.dim() - 2) == viewmats.sizes().slice(0, viewmats.dim() - 3),
-                "means and viewmats batch dimensions must match");
-    TORCH_CHECK(coeffs.dim() == 3, "coeffs must have shape [N, K, D] or [nnz, K, D], got ", coeffs.sizes());
-    TORCH_CHECK(coeffs.size(-1) >= 1, "coeffs last dim D must be >= 1, got ", coeffs.size(-1));
-    TORCH_CHECK((degrees_to_use + 1) * (degrees_to_use + 1) <= coeffs.size(-2),
-                "degrees_to_use requires more SH coefficients than provided; degree ", degrees_to_use, ", coeffs shape ", coeffs.sizes());
-    const bool packed = has(batch_ids) || has(camera_ids) || has(gaussian_ids);
-    TORCH_CHECK(!packed || (has(batch_ids) && has(camera_ids) && has(gaussian_ids)),
-                "batch_ids, camera_ids, and gaussian_ids must either all be provided or all be None");
-    if (packed) {
-        const int64_t nnz = coeffs.size(0);
-        for (const OptTensor *ids : {&batch_ids, &camera_ids, &gaussian_ids}) {
-            TORCH_CHECK((*ids)->dim() == 1 && (*ids)->numel() == nnz, "packed ID tensors must have shape [nnz]");
-            TORCH_CHECK((*ids)->scalar_type() == at::kLong, "packed ID tensors must be int64");
-        }
-        if (has(masks)) TORCH_CHECK(masks->dim() == 1 && masks->numel() == nnz, "packed masks must have shape [nnz]");
-    } else {
-        TORCH_CHECK(means.size(-2) == coeffs.size(0), "means N must match coeffs N in dense mode");
-        if (has(masks)) {
-            at::DimVector mask_shape(viewmats.sizes().slice(0, viewmats.dim() - 2));
-            mask_shape.push_back(means.size(-2));
-            TORCH_CHECK(masks->sizes() == at::IntArrayRef(mask_shape), "dense masks must have shape [..., C, N]");
-        }
-    }
-}
-
-// Rolling-shutter SH (reference SphericalHarmonics.cuh:40-65): view direction = mean + offset, the camera offset R^T t
-// AVERAGED over the two shutter endpoints. An equivalent global-shutter view matrix (identity rotation, t = that average) lets
-// the kernels run unchanged (Python twin: _ops._sh_rs_viewmats / _sh_rs_split).
-Tensor sh_rs_viewmats(const Tensor &viewmats, const Tensor &viewmats_rs)
-{
-    TORCH_CHECK(viewmats_rs.sizes() == viewmats.sizes(), "viewmats_rs must match viewmats shape");
-    TORCH_CHECK(viewmats_rs.scalar_type() == at::kFloat, "viewmats_rs must be float32");
-    auto offset = [](const Tensor &vm) {
-        return at::matmul(vm.narrow(-2, 0, 3).narrow(-1, 0, 3).transpose(-1, -2), vm.narrow(-2, 0, 3).narrow(-1, 3, 1)).squeeze(-1);
-    };
-    Tensor syn = at::zeros_like(viewmats);
-    syn.diagonal(0, -2, -1).fill_(1.0f);
-    syn.narrow(-2, 0, 3).select(-1, 3).copy_(0.5f * (offset(viewmats) + offset(viewmats_rs)));
-    return syn;
-}
-// v_syn[:3, 3] = S = sum over rows of v_dir; each endpoint weighs 1/2: v_R = t (x) S / 2, v_t = R S / 2
-Tensor sh_rs_back(const Tensor &v_syn, const Tensor &vm)
-{
-    const Tensor S = v_syn.narrow(-2, 0, 3).select(-1, 3);
-    Tensor g = at::zeros_like(vm);
-    g.narrow(-2, 0, 3).narrow(-1, 0, 3).copy_(0.5f * vm.narrow(-2, 0, 3).select(-1, 3).unsqueeze(-1) * S.unsqueeze(-2));
-    g.narrow(-2, 0, 3).select(-1, 3).copy_(0.5f * at::matmul(vm.narrow(-2, 0, 3).narrow(-1, 0, 3), S.unsqueeze(-1)).squeeze(-1));
-    return g;
-}
-
-Tensor spherical_harmonics(int64_t degrees_to_use, const Tensor &means_, const Tensor &viewmats_, const Tensor &coeffs_,
-                           const OptTensor &masks_, const OptTensor &batch_ids_, const OptTensor &camera_ids_,
-                           const OptTensor &gaussian_ids_, const OptTensor &viewmats_rs)
-{
-    if (has(viewmats_rs))
-        return spherical_harmonics(degrees_to_use, means_, sh_rs_viewmats(viewmats_, *viewmats_rs), coeffs_, masks_, batch_ids_,
-                                   camera_ids_, gaussian_ids_, OptTensor());
-    check_sh_inputs(degrees_to_use, means_, viewmats_, coeffs_, masks_, batch_ids_, camera_ids_, gaussian_ids_);
-    want_f32(means_, "means"); want_f32(viewmats_, "viewmats");
-    if (coeffs_.scalar_type() == at::kHalf) {
-        // half coefficients, float arithmetic and colours (reference SphericalHarmonicsCUDA.cu:609-638): the band kernels of
-        // csrc/sh_band.hip read dense [N, K, 3] half rows in place; gathered packed rows / D != 3 widen first (rare layouts)
-        if (coeffs_.dim() == 3 && coeffs_.size(-1) == 3 && !has(gaussian_ids_)) {
-            Launch L(means_);
-            const Tensor means = contig(means_), viewmats = contig(viewmats_), coeffs = contig(coeffs_);
-            const OptTensor masks = contig(masks_);
-            const ShDims d = sh_dims(means, viewmats, coeffs, gaussian_ids_);
-            TORCH_CHECK(coeffs.size(0) == d.N, "means N must match coeffs N in dense mode");
-            std::vector<int64_t> shape(viewmats.sizes().begin(), viewmats.sizes().end() - 2);
-            shape.push_back(d.N); shape.push_back(3);
-            Tensor colors = at::empty(shape, means.options());
-            { Timed timed_("gsx_sh_band_fwd", L.stream); check(gsx_sh_band_fwd((int)degrees_to_use, 0, 1, fp(means), fp(viewmats), coeffs.const_data_ptr(),
-                                  has(masks) ? (const uint8_t *)masks->const_data_ptr<bool>() : nullptr, nullptr, nullptr, nullptr,
-                                  (uint32_t)d.B, (uint32_t)d.C, (uint32_t)d.N, -1, (uint32_t)d.K, mp<float>(colors), L.stream),
-                  "gsx_sh_band_fwd"); }
-            return colors;
-        }
-        return spherical_harmonics(degrees_to_use, means_, viewmats_, coeffs_.to(at::kFloat), masks_, batch_ids_, camera_ids_,
-                                   gaussian_ids_, viewmats_rs);
-    }
-    want_f32(coeffs_, "coeffs");
-    Launch L(means_);
-    const Tensor means = contig(means_), viewmats = contig(viewmats_), coeffs = contig(coeffs_);
-    const OptTensor masks = contig(masks_), bi = contig(batch_ids_), ci = contig(camera_ids_), gi = contig(gaussian_ids_);
-    const ShDims d = sh_dims(means, viewmats, coeffs, gi);
-    Tensor colors;
-    int64_t nnz = -1;
-    if (d.packed) {
-        nnz = gi->size(0);
-        colors = at::empty({nnz, d.D}, means.options());
-    } else {
-        TORCH_CHECK(coeffs.size(0) == d.N, "means N must match coeffs N in dense mode");
-        std::vector<int64_t> shape(viewmats.sizes().begin(), viewmats.sizes().end() - 2);
-        shape.push_back(d.N); shape.push_back(d.D);
-        colors = at::empty(shape, means.options());
-    }
-    { Timed timed_("gsx_sh_fwd", L.stream); check(gsx_sh_fwd((int)degrees_to_use, fp(means), fp(viewmats), fp(coeffs), has(masks) ? (const uint8_t *)masks->const_data_ptr<bool>() : nullptr,
-                     cp<int64_t>(bi), cp<int64_t>(ci), cp<int64_t>(gi), (uint32_t)d.B, (uint32_t)d.C, (uint32_t)d.N, nnz, 1,
-                     (uint32_t)d.K, (uint32_t)d.D, nullptr, 0, mp<float>(colors), L.stream),
-          "gsx_sh_fwd"); }
-    return colors;
-}
-
-std::tuple<Tensor, OptTensor, OptTensor, OptTensor>
-spherical_harmonics_bwd(int64_t degrees_to_use, const Tensor &means_, const Tensor &viewmats_, const Tensor &coeffs_,
-                        const OptTensor &masks_, const OptTensor &batch_ids_, const OptTensor &camera_ids_,
-                        const OptTensor &gaussian_ids_, const OptTensor &viewmats_rs, const Tensor &v_colors_,
-                        bool compute_v_means, bool compute_v_viewmats, bool compute_v_viewmats_rs)
-{
-    if (has(viewmats_rs)) {
-        auto r = spherical_harmonics_bwd(degrees_to_use, means_, sh_rs_viewmats(viewmats_, *viewmats_rs), coeffs_, masks_, batch_ids_,
-                                         camera_ids_, gaussian_ids_, OptTensor(), v_colors_, compute_v_means,
-                                         compute_v_viewmats || compute_v_viewmats_rs, false);
-        OptTensor v_vm, v_rs;
-        if (std::get<2>(r).has_value()) {
-            if (compute_v_viewmats) v_vm = sh_rs_back(*std::get<2>(r), viewmats_);
-            if (compute_v_viewmats_rs) v_rs = sh_rs_back(*std::get<2>(r), *viewmats_rs);
-        }
-        return {std::get<0>(r), std::get<1>(r), v_vm, v_rs};
-    }
-    TORCH_CHECK(!compute_v_viewmats_rs, "compute_v_viewmats_rs needs viewmats_rs");
-    if (coeffs_.scalar_type() == at::kHalf) { // see spherical_harmonics: v_coeffs comes back in the coefficients' own type
-        if (coeffs_.dim() == 3 && coeffs_.size(-1) == 3 && !has(gaussian_ids_)) {
-            Launch L(means_);
-            const Tensor means = contig(means_), viewmats = contig(viewmats_), coeffs = contig(coeffs_), vcol = contig(v_colors_);
-            const OptTensor masks = contig(masks_);
-            const ShDims d = sh_dims(means, viewmats, coeffs, gaussian_ids_);
-            Tensor v_coeffs = at::empty_like(coeffs);
-            OptTensor v_means, v_viewmats;
-            if (compute_v_means) v_means = at::empty_like(means);
-            Tensor v_dirs;
-            if (compute_v_viewmats) v_dirs = at::zeros({d.B * d.C * d.N, 3}, means.options());
-            { Timed timed_("gsx_sh_band_bwd", L.stream); check(gsx_sh_band_bwd((int)degrees_to_use, 0, 1, fp(means), fp(viewmats), coeffs.const_data_ptr(),
-                                  has(masks) ? (const uint8_t *)masks->const_data_ptr<bool>() : nullptr, (uint32_t)d.B, (uint32_t)d.C,
-                                  (uint32_t)d.N, -1, (uint32_t)d.K, vcol.const_data_ptr<float>(), nullptr, v_coeffs.mutable_data_ptr(),
-                                  v_means ? mp<float>(*v_means) : nullptr, v_dirs.defined() ? mp<float>(v_dirs) : nullptr, L.stream),
-                  "gsx_sh_band_bwd"); }
-            if (compute_v_viewmats) {
-                const Tensor S = v_dirs.view({d.B * d.C, d.N, 3}).sum(1);
-                const Tensor vm = viewmats.reshape({d.B * d.C, 4, 4});
-                const Tensor R = vm.slice(1, 0, 3).slice(2, 0, 3), t = vm.slice(1, 0, 3).select(2, 3);
-                Tensor v_vm = at::zeros_like(vm);
-                v_vm.slice(1, 0, 3).slice(2, 0, 3).copy_(t.unsqueeze(2) * S.unsqueeze(1));
-                v_vm.slice(1, 0, 3).select(2, 3).copy_(at::einsum("cij,cj->ci", {R, S}));
-                v_viewmats = v_vm.reshape(viewmats.sizes());
-            }
-            return {v_coeffs, v_means, v_viewmats, OptTensor()};
-        }
-        auto r = spherical_harmonics_bwd(degrees_to_use, means_, viewmats_, coeffs_.to(at::kFloat), masks_, batch_ids_, camera_ids_,
-                                         gaussian_ids_, viewmats_rs, v_colors_, compute_v_means, compute_v_viewmats, false);
-        return {std::get<0>(r).to(at::kHalf), std::get<1>(r), std::get<2>(r), std::get<3>(r)};
-    }
-    Launch L(means_);
-    const Tensor means = contig(means_), viewmats = contig(viewmats_), coeffs = contig(coeffs_);
-    const OptTensor masks = contig(masks_), bi = contig(batch_ids_), ci = contig(camera_ids_), gi = contig(gaussian_ids_);
-    const ShDims d = sh_dims(means, viewmats, coeffs, gi);
-    auto [vcol, vstride] = row_view(v_colors_, d.D); // may be a column view of the compositing kernel's gradient rows
-    Tensor v_coeffs = at::empty_like(coeffs);        // gathered coefficient rows: fully written by the kernel
-    OptTensor v_means, v_viewmats;
-    if (compute_v_means) {
-        const bool full_write = d.D == 3 && d.N > 0 && !d.packed; // sh3_bwd_dense_kernel stores every (b, g)
-        v_means = full_write ? at::empty_like(means) : at::zeros_like(means);
-    }
-    const int64_t nnz = d.packed ? gi->size(0) : -1;
-    Tensor v_dirs;
-    if (compute_v_viewmats) v_dirs = at::zeros({d.packed ? nnz : d.B * d.C * d.N, 3}, means.options());
-    { Timed timed_("gsx_sh_bwd", L.stream); check(gsx_sh_bwd((int)degrees_to_use, fp(means), fp(viewmats), fp(coeffs), has(masks) ? (const uint8_t *)masks->const_data_ptr<bool>() : nullptr,
-                     cp<int64_t>(bi), cp<int64_t>(ci), cp<int64_t>(gi), (uint32_t)d.B, (uint32_t)d.C, (uint32_t)d.N, nnz, 1,
-                     (uint32_t)d.K, (uint32_t)d.D, nullptr, nullptr, vcol.const_data_ptr<float>(), vstride, nullptr,
-                     mp<float>(v_coeffs), v_means ? mp<float>(*v_means) : nullptr, v_dirs.defined() ? mp<float>(v_dirs) : nullptr,
-                     L.stream),
-          "gsx_sh_bwd"); }
-    if (compute_v_viewmats) {
-        // dir = mean + R^T t  =>  v_R = t (x) sum_rows v_dir,  v_t = R sum_rows v_dir per camera (small host-side tensors)
-        Tensor S;
-        if (d.packed) {
-            S = at::zeros({d.B * d.C, 3}, means.options());
-            S.index_add_(0, *bi * d.C + *ci, v_dirs);
-        } else {
-            S = v_dirs.view({d.B * d.C, d.N, 3}).sum(1);
-        }
-        const Tensor vm = viewmats.reshape({d.B * d.C, 4, 4});
-        const Tensor R = vm.slice(1, 0, 3).slice(2, 0, 3), t = vm.slice(1, 0, 3).select(2, 3);
-        Tensor v_vm = at::zeros_like(vm);
-        v_vm.slice(1, 0, 3).slice(2, 0, 3).copy_(t.unsqueeze(2) * S.unsqueeze(1));
-        v_vm.slice(1, 0, 3).select(2, 3).copy_(at::einsum("cij,cj->ci", {R, S}));
-        v_viewmats = v_vm.reshape(viewmats.sizes());
-    }
-    return {v_coeffs, v_means, v_viewmats, OptTensor()};
-}
-
 // ---- longest tile list of an intersection result, for the compositing calls that consume it ---------------------------
 // A caller that drives the STAGE ops itself (the reference's isect_tiles -> isect_offset_encode -> rasterize_to_pixels, e.g.
 // its own Python over this shim) has no orchestrator to carry the hint: the intersection notes the longest list of the result
@@ -663,144 +371,6 @@ static bool seg_reuse_env()
 // ---- tile intersection --------------------------------------------------------------------------------------------------
 Tensor bytes(int64_t n, const Tensor &like) { return at::empty({n < 8 ? 8 : n}, like.options().dtype(at::kByte)); }
 
-std::tuple<Tensor, Tensor, Tensor>
-intersect_tile(const Tensor &means2d_, const Tensor &radii_, const Tensor &depths_, const OptTensor &conics_,
-               const OptTensor &opacities_, const OptTensor &image_ids_, const OptTensor &gaussian_ids, std::optional<int64_t> n_images,
-               int64_t tile_size, int64_t tile_w, int64_t tile_h, bool sort, bool segmented)
-{
-    (void)gaussian_ids; // the global sort is used (results are identical to the segmented one), but the reference's refusal of
-    // segmented + packed (Intersect.cpp:207-211) is part of the contract
-    TORCH_CHECK(!(has(image_ids_) && segmented), "segmented sort is not supported for packed inputs");
-    const bool f64 = means2d_.scalar_type() == at::kDouble; // radius boxes in double, depth narrowed to float32 in the key
-    if (f64) {
-        TORCH_CHECK(!has(conics_) && !has(opacities_), "gsplat_amd: intersect_tile with float64 rows supports the "
-                         "radius-box test only (conics / opacities select the exact test, which is computed in fp32)");
-    } else {
-        want_f32(means2d_, "means2d"); want_f32(depths_, "depths"); want_f32(conics_, "conics"); want_f32(opacities_, "opacities");
-    }
-    Launch L(means2d_);
-    const bool packed = has(image_ids_);
-    const Tensor means2d = contig(means2d_), depths = contig(f64 ? depths_.to(at::kDouble) : depths_);
-    const Tensor radii = contig(radii_.scalar_type() == at::kInt ? radii_ : radii_.to(at::kInt));
-    const OptTensor conics = contig(conics_), opac = contig(opacities_), image_ids = contig(image_ids_);
-    int64_t rows, n_per, I;
-    std::vector<int64_t> out_shape;
-    if (packed) {
-        TORCH_CHECK(n_images.has_value(), "n_images is required when packed");
-        rows = means2d.size(0); n_per = 1; I = *n_images;
-        out_shape = {rows};
-    } else {
-        auto image_dims = means2d.sizes().slice(0, means2d.dim() - 2);
-        I = prod(image_dims); n_per = means2d.size(-2); rows = I * n_per;
-        out_shape.assign(means2d.sizes().begin(), means2d.sizes().end() - 1);
-    }
-    const uint32_t tile_bits = bits_for_count(tile_w * tile_h), image_bits = bits_for_count(I);
-    TORCH_CHECK(tile_bits + image_bits <= 32, "intersect_tile: tile id bits (", tile_bits, ") + image id bits (", image_bits,
-                ") exceed the 32 bits available above the depth in the 64-bit sort key");
-    Tensor tiles_per_gauss = at::empty(out_shape, means2d.options().dtype(at::kInt));
-    auto none = [&]() {
-        return std::make_tuple(tiles_per_gauss, at::empty({0}, means2d.options().dtype(at::kLong)),
-                               at::empty({0}, means2d.options().dtype(at::kInt)));
-    };
-    if (rows == 0) return none();
-    const uint32_t uI = (uint32_t)I, uts = (uint32_t)tile_size, utw = (uint32_t)tile_w, uth = (uint32_t)tile_h;
-    // the grand total comes back through pinned host memory (the one host sync of this op: Intersect.cpp:258-259)
-    Tensor host_total = at::empty({2}, at::TensorOptions().dtype(at::kLong).pinned_memory(true)); // [n_isects, longest tile list]
-    host_total.mutable_data_ptr<int64_t>()[1] = 0;
-    int64_t *const host_longest = host_total.mutable_data_ptr<int64_t>() + 1;
-    auto hip_stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(means2d.device().index());
-    if (sort && !f64 && gsx_isect_fused_supported(uI, utw, uth, packed ? 1 : 0)) {
-        Tensor offsets = at::empty({I * tile_w * tile_h}, means2d.options().dtype(at::kInt));
-        int64_t M = GSX_ISECT_RETRY;
-        if (gsx_isect_binned_should_try(rows, uI, utw, uth, packed ? 1 : 0)) { // the one decision of this intersection
-            // tile-owner-major path (csrc/isect_binned.hip); GSX_ISECT_RETRY = its entry workspace was too small
-            Tensor count_ws = bytes(gsx_isect_binned_count_workspace_bytes(rows, uI, utw, uth), means2d);
-            { Timed timed_("gsx_isect_binned_count", L.stream); check(gsx_isect_binned_count(fp(means2d), cp<int32_t>(radii), fp(depths), fp(conics), fp(opac), nullptr, rows, uI,
-                                         uts, utw, uth, mp<int32_t>(tiles_per_gauss), mp<int32_t>(offsets),
-                                         host_total.mutable_data_ptr<int64_t>(), host_longest, count_ws.mutable_data_ptr(), count_ws.numel(), L.stream),
-                  "gsx_isect_binned_count"); }
-            hip_stream.synchronize();
-            M = *host_total.const_data_ptr<int64_t>();
-            if (M != GSX_ISECT_RETRY) {
-                TORCH_CHECK(M < (1ll << 31), "intersect_tile: ", M, " intersections overflow the int32 index space");
-                Tensor ids = at::empty({M}, means2d.options().dtype(at::kLong)), flat = at::empty({M}, means2d.options().dtype(at::kInt));
-                if (M == 0) return {tiles_per_gauss, ids, flat};
-                Tensor ws = bytes(gsx_isect_binned_emit_workspace_bytes(M), means2d);
-                { Timed timed_("gsx_isect_binned_emit_sort", L.stream); check(gsx_isect_binned_emit_sort(rows, uI, uts, utw, uth, count_ws.mutable_data_ptr(), count_ws.numel(),
-                                                 cp<int32_t>(offsets), M, *host_longest, mp<int64_t>(ids), mp<int32_t>(flat), ws.mutable_data_ptr(), ws.numel(), L.stream),
-                      "gsx_isect_binned_emit_sort"); }
-                note_longest(flat, *host_longest);
-                return {tiles_per_gauss, ids, flat};
-            }
-            gsx_isect_binned_note_retry(rows, uI, utw, uth); // sent back: not tried again for the next 63 calls of this shape
-        }
-        Tensor count_ws = bytes(gsx_isect_fused_count_workspace_bytes(rows, uI, utw, uth), means2d);
-        { Timed timed_("gsx_isect_fused_count", L.stream); check(gsx_isect_fused_count(fp(means2d), cp<int32_t>(radii), fp(conics), fp(opac), nullptr, rows, uI, uts, utw, uth,
-                                    mp<int32_t>(tiles_per_gauss), mp<int32_t>(offsets), host_total.mutable_data_ptr<int64_t>(), host_longest,
-                                    count_ws.mutable_data_ptr(), count_ws.numel(), L.stream),
-              "gsx_isect_fused_count"); }
-        hip_stream.synchronize();
-        M = *host_total.const_data_ptr<int64_t>();
-        TORCH_CHECK(M < (1ll << 31), "intersect_tile: ", M, " intersections overflow the int32 index space");
-        Tensor ids = at::empty({M}, means2d.options().dtype(at::kLong)), flat = at::empty({M}, means2d.options().dtype(at::kInt));
-        if (M == 0) return {tiles_per_gauss, ids, flat};
-        Tensor ws = bytes(gsx_isect_fused_emit_workspace_bytes(M, uI, utw, uth), means2d);
-        { Timed timed_("gsx_isect_fused_emit_sort", L.stream); check(gsx_isect_fused_emit_sort(fp(means2d), cp<int32_t>(radii), fp(depths), fp(conics), fp(opac), nullptr, rows, uI, uts,
-                                        utw, uth, count_ws.mutable_data_ptr(), count_ws.numel(), cp<int32_t>(offsets), M,
-                                        mp<int64_t>(ids), mp<int32_t>(flat), ws.mutable_data_ptr(), ws.numel(), L.stream),
-              "gsx_isect_fused_emit_sort"); }
-        note_longest(flat, *host_longest);
-        return {tiles_per_gauss, ids, flat};
-    }
-    if (f64) {
-        Timed timed_("gsx_isect_count_f64", L.stream);
-        check(gsx_isect_count_f64(cp<double>(means2d), cp<int32_t>(radii), cp<int64_t>(image_ids), rows, (uint32_t)n_per, uI, uts,
-                                  utw, uth, mp<int32_t>(tiles_per_gauss), L.stream),
-              "gsx_isect_count_f64");
-    } else
-    { Timed timed_("gsx_isect_count", L.stream); check(gsx_isect_count(fp(means2d), cp<int32_t>(radii), fp(conics), fp(opac), cp<int64_t>(image_ids), rows, (uint32_t)n_per, uI,
-                          uts, utw, uth, mp<int32_t>(tiles_per_gauss), L.stream),
-          "gsx_isect_count"); }
-    Tensor cum = at::empty({rows}, means2d.options().dtype(at::kLong));
-    {
-        Tensor ws = bytes(gsx_scan_workspace_bytes(rows), means2d);
-        { Timed timed_("gsx_scan_i32", L.stream); check(gsx_scan_i32(cp<int32_t>(tiles_per_gauss), rows, mp<int64_t>(cum), ws.mutable_data_ptr(), ws.numel(), L.stream),
-              "gsx_scan_i32"); }
-    }
-    host_total.copy_(cum.slice(0, rows - 1, rows), /*non_blocking=*/true);
-    hip_stream.synchronize();
-    const int64_t M = *host_total.const_data_ptr<int64_t>();
-    TORCH_CHECK(M < (1ll << 31), "intersect_tile: ", M, " intersections overflow the int32 index space");
-    Tensor ids = at::empty({M}, means2d.options().dtype(at::kLong)), flat = at::empty({M}, means2d.options().dtype(at::kInt));
-    if (M == 0) return {tiles_per_gauss, ids, flat};
-    if (f64) {
-        Timed timed_("gsx_isect_emit_f64", L.stream);
-        check(gsx_isect_emit_f64(cp<double>(means2d), cp<int32_t>(radii), cp<double>(depths), cp<int64_t>(image_ids),
-                                 cp<int64_t>(cum), rows, (uint32_t)n_per, uI, uts, utw, uth, mp<int64_t>(ids), mp<int32_t>(flat),
-                                 L.stream),
-              "gsx_isect_emit_f64");
-    } else
-    { Timed timed_("gsx_isect_emit", L.stream); check(gsx_isect_emit(fp(means2d), cp<int32_t>(radii), fp(depths), fp(conics), fp(opac), cp<int64_t>(image_ids),
-                         cp<int64_t>(cum), rows, (uint32_t)n_per, uI, uts, utw, uth, mp<int64_t>(ids), mp<int32_t>(flat), L.stream),
-          "gsx_isect_emit"); }
-    if (!sort) return {tiles_per_gauss, ids, flat};
-    Tensor ids2 = at::empty_like(ids), flat2 = at::empty_like(flat);
-    if (gsx_isect_tile_sort_supported(uI, utw, uth)) {
-        Tensor ws = bytes(gsx_isect_tile_sort_workspace_bytes(M, uI, utw, uth), means2d);
-        { Timed timed_("gsx_isect_tile_sort", L.stream); check(gsx_isect_tile_sort(cp<int64_t>(ids), cp<int32_t>(flat), M, uI, utw, uth, mp<int64_t>(ids2), mp<int32_t>(flat2),
-                                  ws.mutable_data_ptr(), ws.numel(), L.stream),
-              "gsx_isect_tile_sort"); }
-        return {tiles_per_gauss, ids2, flat2};
-    }
-    Tensor ws = bytes(gsx_sort_pairs_workspace_bytes(M), means2d);
-    int in_alt = 0;
-    { Timed timed_("gsx_sort_pairs", L.stream); check(gsx_sort_pairs(mp<int64_t>(ids), mp<int32_t>(flat), mp<int64_t>(ids2), mp<int32_t>(flat2), M,
-                         (int)(32 + tile_bits + image_bits), ws.mutable_data_ptr(), ws.numel(), &in_alt, L.stream),
-          "gsx_sort_pairs"); }
-    if (in_alt) return {tiles_per_gauss, ids2, flat2};
-    return {tiles_per_gauss, ids, flat};
-}
-
 Tensor intersect_offset(const Tensor &isect_ids_, int64_t I, int64_t tile_w, int64_t tile_h)
 {
     Launch L(isect_ids_);
@@ -893,70 +463,9 @@ rasterize_to_pixels_3dgs(const Tensor &means2d_, const Tensor &conics_, const Te
     return {renders, alphas, holder, last_ids};
 }
 
-std::tuple<OptTensor, Tensor, Tensor, Tensor, Tensor, OptTensor>
-rasterize_to_pixels_3dgs_bwd(const Tensor &means2d_, const Tensor &conics_, const Tensor &colors_, const Tensor &opacities_,
-                             const OptTensor &backgrounds_, const OptTensor &masks_, const Tensor &tile_offsets_,
-                             const Tensor &flatten_ids_, const Tensor &render_alphas_, const Tensor &last_ids_, int64_t width,
-                             int64_t height, int64_t tile_size, bool absgrad, const Tensor &v_render_colors_,
-                             const Tensor &v_render_alphas_, bool compute_v_backgrounds)
-{
-    Launch L(means2d_);
-    const RasterDims r = raster_dims(tile_offsets_, colors_);
-    const Tensor means2d = contig(means2d_), conics = contig(conics_), colors = contig(colors_), opac = contig(opacities_);
-    const OptTensor bg = contig(backgrounds_), masks = contig(masks_);
-    const Tensor offsets = contig(tile_offsets_), flat = contig(flatten_ids_), ra = contig(render_alphas_), li = contig(last_ids_);
-    const Tensor v_rc = contig(v_render_colors_);
-    const Tensor v_ra = v_render_alphas_.defined() ? contig(v_render_alphas_) : Tensor(); // undefined = zeros
-    // ONE zero-filled array-of-structures buffer [R][6 (+2) + D]; the gradients are COLUMN VIEWS of it (gsplat_amd.h)
-    const int64_t R = opac.numel(), geo = absgrad ? 8 : 6;
-    int64_t longest = g_long_tile_hint; // set by the autograd formula around this call (gsplat_amd/_autograd.py)
-    g_long_tile_hint = 0;
-    if (longest == 0) longest = lookup_longest(flatten_ids_); // e.g. the reference's own autograd formula
-    const bool segmented = kSegLen > 0 && !absgrad && r.D <= 4 && tile_size == 16
-        && longest > gsx_raster3d_seg_cut(flat.numel(), (uint32_t)r.I, (uint32_t)r.tw, (uint32_t)r.th, (uint32_t)kSegLen);
-    // the per-tile launch zero-fills the rows itself (inside its tile-order kernel: gsx_raster3d_bwd_fill)
-    Tensor rows = segmented ? at::zeros({R, geo + r.D}, means2d.options()) : at::empty({R, geo + r.D}, means2d.options());
-    if (segmented) {
-        Tensor ws = at::empty({gsx_raster3d_bwd_seg_workspace_bytes(flat.numel(), (uint32_t)r.I, (uint32_t)r.tw, (uint32_t)r.th, (uint32_t)r.D,
-                                                                  (uint32_t)kSegLen)}, means2d.options().dtype(at::kByte));
-        // the forward call's workspace, when this process still has it (noted under last_ids): no pre-pass
-        const Tensor fws = seg_reuse_env() ? lookup_seg_workspace(last_ids_, flat.numel(), r.D, kSegLen,
-                                                                  {means2d_, conics_, colors_, opacities_, tile_offsets_, flatten_ids_})
-                                           : Tensor();
-        Timed timed_("gsx_raster3d_bwd", L.stream);
-        check(gsx_raster3d_bwd_seg_reuse(fp(means2d), fp(conics), fp(colors), fp(opac), fp(bg),
-                                   masks ? (const uint8_t *)masks->const_data_ptr<bool>() : nullptr, cp<int32_t>(offsets),
-                                   cp<int32_t>(flat), fp(ra), cp<int32_t>(li), fp(v_rc), fp(v_ra), (uint32_t)r.I, (uint32_t)flat.numel(),
-                                   (uint32_t)r.D, (uint32_t)width, (uint32_t)height, (uint32_t)tile_size, (uint32_t)r.tw, (uint32_t)r.th,
-                                   mp<float>(rows), (uint32_t)(geo + r.D), (uint32_t)kSegLen,
-                                   fws.defined() ? fws.const_data_ptr() : nullptr, fws.defined() ? fws.numel() : 0,
-                                   ws.mutable_data_ptr(), ws.numel(), L.stream),
-              "gsx_raster3d_bwd_seg_reuse");
-    } else
-    {
-        // workspace for the longest-first tile order of the launch (csrc/raster3d_bwd.hip: "longest tiles first")
-        Tensor ws = at::empty({gsx_raster3d_bwd_workspace_bytes((uint32_t)r.I, (uint32_t)r.tw, (uint32_t)r.th)}, means2d.options().dtype(at::kByte));
-        Timed timed_("gsx_raster3d_bwd", L.stream);
-        check(gsx_raster3d_bwd_fill(fp(means2d), fp(conics), fp(colors), fp(opac), fp(bg),
-                                  masks ? (const uint8_t *)masks->const_data_ptr<bool>() : nullptr, cp<int32_t>(offsets),
-                                  cp<int32_t>(flat), fp(ra), cp<int32_t>(li), fp(v_rc), fp(v_ra), (uint32_t)r.I, (uint32_t)flat.numel(),
-                                  (uint32_t)r.D, (uint32_t)width, (uint32_t)height, (uint32_t)tile_size, (uint32_t)r.tw, (uint32_t)r.th,
-                                  absgrad ? 1 : 0, mp<float>(rows), (uint32_t)(geo + r.D), R, (int64_t)-1, (int64_t)1, ws.mutable_data_ptr(), ws.numel(),
-                                  L.stream),
-              "gsx_raster3d_bwd");
-    }
-    Tensor v_means2d = rows.slice(1, 0, 2).view(means2d.sizes()), v_conics = rows.slice(1, 2, 5).view(conics.sizes());
-    Tensor v_opac = rows.select(1, 5).view(opac.sizes()), v_colors = rows.slice(1, geo, geo + r.D).view(colors.sizes());
-    OptTensor v_abs, v_bg;
-    if (absgrad) v_abs = rows.slice(1, 6, 8).view(means2d.sizes());
-    if (has(bg) && compute_v_backgrounds) v_bg = (v_rc * (1.0 - ra)).sum(at::IntArrayRef({-3, -2})); // Rasterization.cpp:567-577
-    return {v_abs, v_means2d, v_conics, v_colors, v_opac, v_bg};
-}
-
-// ---- the two halves of the fused intersection, for the orchestrators (rendering.py) --------------------------------------
-// intersect_tile above blocks on the intersection count between its halves. The orchestrators enqueue the SH kernels in
-// between instead (gsplat_amd/_ops.py: isect_begin / isect_finish); these are the same two halves as private ops
-// (namespace gsplat_amd: not part of the reference's surface). The count travels through a pinned host word initialised to a
+// ---- the two halves of the fused intersection (gsplat_amd/_ops.py: isect_begin / isect_finish, behind intersect_tile) ------
+// The orchestrators (rendering.py) enqueue the SH kernels between the halves instead of blocking on the intersection count;
+// private ops (namespace gsplat_amd: not part of the reference's surface). The count travels through a pinned host word initialised to a
 // sentinel: the second half polls it - no event, no stream synchronisation, and the kernels enqueued in between keep running.
 std::tuple<Tensor, Tensor, Tensor, Tensor>
 isect_fused_begin(const Tensor &means2d, const Tensor &radii, const Tensor &depths, const OptTensor &conics, const OptTensor &opac,
@@ -1050,8 +559,7 @@ isect_fused_finish(const Tensor &means2d, const Tensor &radii, const Tensor &dep
     return {ids, flat};
 }
 
-// ---- 2DGS: the two forward ops on the critical host path of rasterization_2dgs (the backward bodies stay in _ops.py: the
-// GPU has the whole compositing backward queued while they run) -------------------------------------------------------------
+// ---- 2DGS: the two forward ops on the critical host path of rasterization_2dgs ----------------------------------------------
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor>
 projection_2dgs_fused(const Tensor &means_, const Tensor &quats_, const Tensor &scales_, const Tensor &viewmats_, const Tensor &Ks_,
                       int64_t width, int64_t height, double eps2d, double near_plane, double far_plane, double radius_clip)
@@ -1063,7 +571,6 @@ projection_2dgs_fused(const Tensor &means_, const Tensor &quats_, const Tensor &
     TORCH_CHECK(means_.size(-1) == 3 && quats_.dim() >= 2 && quats_.size(-2) == N && quats_.size(-1) == 4
                           && scales_.dim() >= 2 && scales_.size(-2) == N && scales_.size(-1) == 3,
                       "projection_2dgs: bad shapes means ", means_.sizes(), " quats ", quats_.sizes(), " scales ", scales_.sizes());
-    Launch L(means_);
     const Tensor means = contig(means_), quats = contig(quats_), scales = contig(scales_), viewmats = contig(viewmats_),
                  Ks = contig(Ks_);
     const int64_t B = prod(means.sizes().slice(0, means.dim() - 2)), C = viewmats.size(-3);
@@ -1077,6 +584,8 @@ projection_2dgs_fused(const Tensor &means_, const Tensor &quats_, const Tensor &
     Tensor radii = at::empty(with({2}), means.options().dtype(at::kInt)), means2d = at::empty(with({2}), means.options());
     Tensor depths = at::empty(shape, means.options()), rt = at::empty(with({3, 3}), means.options());
     Tensor normals = at::empty(with({3}), means.options());
+    if (B * C * N == 0) return {radii, means2d, depths, rt, normals}; // nothing to launch (before the device is touched)
+    Launch L(means_);
     { Timed timed_("gsx_project_2dgs_fwd", L.stream); check(gsx_project_2dgs_fwd(fp(means), fp(quats), fp(scales), fp(viewmats), fp(Ks), (uint32_t)B, (uint32_t)C, (uint32_t)N,
                                (uint32_t)width, (uint32_t)height, (float)near_plane, (float)far_plane, (float)radius_clip,
                                mp<int32_t>(radii), mp<float>(means2d), mp<float>(depths), mp<float>(rt), mp<float>(normals),
@@ -1150,7 +659,8 @@ TORCH_LIBRARY(gsplat_amd, m)
           "int tile_w, int tile_h, int[] out_shape) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("isect_fused_finish(Tensor means2d, Tensor radii, Tensor depths, Tensor? conics, Tensor? opacities, int rows, int n_images, "
           "int tile_size, int tile_w, int tile_h, Tensor count_ws, Tensor offsets, Tensor host_total, Tensor tiles_per_gauss) -> (Tensor, Tensor)");
-    // the Python op bodies (GSPLAT_AMD_COMPILED_OPS=0, A/B kernel libraries) share the compiled bodies' notes
+    // the notes, for the Python op bodies: the non-fused intersection notes its longest list, the compositing backward looks
+    // up the forward's segment workspace
     m.def("note_longest(Tensor flatten_ids, int longest) -> ()");
     m.def("lookup_longest(Tensor flatten_ids) -> int");
     m.def("note_seg_workspace(Tensor last_ids, Tensor ws, int n_isects, int cdim, int seg_len, Tensor[] inputs) -> ()");
@@ -1176,14 +686,9 @@ TORCH_LIBRARY_IMPL(gsplat, CUDA, m)
 {
     using namespace gsplat_amd;
     m.impl("projection_ewa_3dgs_fused", &projection_ewa_3dgs_fused);
-    m.impl("projection_ewa_3dgs_fused_bwd", &projection_ewa_3dgs_fused_bwd);
     m.impl("projection_ewa_3dgs_packed", &projection_ewa_3dgs_packed);
-    m.impl("spherical_harmonics", &spherical_harmonics);
-    m.impl("spherical_harmonics_bwd", &spherical_harmonics_bwd);
-    m.impl("intersect_tile", &intersect_tile);
     m.impl("intersect_offset", &intersect_offset);
     m.impl("rasterize_to_pixels_3dgs", &rasterize_to_pixels_3dgs);
-    m.impl("rasterize_to_pixels_3dgs_bwd", &rasterize_to_pixels_3dgs_bwd);
     m.impl("projection_2dgs_fused", &projection_2dgs_fused);
     m.impl("rasterize_to_pixels_2dgs", &rasterize_to_pixels_2dgs);
 }
@@ -1222,12 +727,4 @@ extern "C" const char *gsx_torch_profile_end()
     }
     g_prof.clear();
     return out.c_str();
-}
-
-// the ops above, for gsplat_amd/_ops.py (which keeps its Python body for every op NOT named here)
-extern "C" const char *gsx_torch_compiled_ops()
-{
-    return "projection_ewa_3dgs_fused projection_ewa_3dgs_fused_bwd projection_ewa_3dgs_packed spherical_harmonics spherical_harmonics_bwd "
-           "intersect_tile intersect_offset rasterize_to_pixels_3dgs rasterize_to_pixels_3dgs_bwd "
-           "projection_2dgs_fused rasterize_to_pixels_2dgs";
 }

@@ -51,7 +51,7 @@ def build_config() -> dict:
 
 def built_3dgut_subset() -> bool:
     """True when the 3DGUT ops (see build_config) are loadable - not a key of build_config(): its key set is ext.cpp's."""
-    return _ops.COMPOSITE_UNAVAILABLE is None and "rasterize_to_pixels_from_world_3dgs" in _ops.CLASS_SCHEMAS
+    return "rasterize_to_pixels_from_world_3dgs" in _ops.CLASS_SCHEMAS
 
 
 def null() -> None:  # ext.cpp:82

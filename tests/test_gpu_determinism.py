@@ -85,7 +85,7 @@ def test_forward_is_bit_reproducible_across_processes_and_history():
 
     code = _SCRIPT % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
     procs = []
-    for noise, env in (("0", {}), ("1", {}), ("1", {"GSPLAT_AMD_COMPILED_OPS": "0"})):
+    for noise, env in (("0", {}), ("1", {})):
         procs.append(subprocess.Popen([sys.executable, "-c", code, "50", noise], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                       text=True, env=dict(os.environ, **env)))
     mine = render_hashes(gsplat_amd, 50, True)  # this process: whatever the suite ran before + interleaved other scenes

@@ -659,7 +659,7 @@ def test_rasterize_bwd_reads_cotangent_views_in_place(G, kind):
     _, ids, fl = G.isect_tiles(m2, rad, d, 16, tw, th, conics=con, opacities=op)
     off = G.isect_offset_encode(ids, 2, tw, th)
     colors = torch.rand(2, 5000, 3, device=DEV)
-    rc, ra, _, last = _ops.rasterize_to_pixels_3dgs(m2, con, colors, op, None, None, W, H, 16, off, fl, False, False)
+    rc, ra, _, last = torch.ops.gsplat.rasterize_to_pixels_3dgs(m2, con, colors, op, None, None, W, H, 16, off, fl, False, False)
     if kind == "expanded-scalar":
         v = torch.tensor(0.75, device=DEV).expand(rc.shape)
     elif kind == "channel-slice":

@@ -514,7 +514,7 @@ def test_distributed_single_rank_matches_local(G, packed, force_exchange, monkey
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         import socket
 
-        with socket.socket() as sk:  # a free port: this test also runs inside test_gpu_python_bodies' subprocess, concurrently
+        with socket.socket() as sk:  # a free port: another process may run this test concurrently
             sk.bind(("127.0.0.1", 0))
             os.environ["MASTER_PORT"] = str(sk.getsockname()[1])
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")

@@ -81,7 +81,12 @@ def test_raster3d_bwd_variants_match_the_default(variant):
         if order:
             env["GSX_RASTER3D_BWD_ORDER"] = order
         if os.environ.get("GSX_VARIANT_LIB"):  # an alternative build of the library for the variant side (A/B builds)
-            env["GSPLAT_AMD_LIB"] = os.environ["GSX_VARIANT_LIB"]
+            # tools/mkvariant.sh builds libgsplat_amd_<name>.so and libgsplat_amd_torch_<name>.so: the variant side's
+            # compiled op bodies call the variant's kernels
+            lib = os.environ["GSX_VARIANT_LIB"]
+            env["GSPLAT_AMD_LIB"] = lib
+            env["GSPLAT_AMD_TORCH_LIB"] = os.path.join(os.path.dirname(lib), os.path.basename(lib).replace(
+                "libgsplat_amd", "libgsplat_amd_torch", 1))
         r = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         alt = dict(np.load(path))

@@ -149,31 +149,6 @@ def test_elem_view_reads_single_columns_in_place():
     assert st == 1 and t.is_contiguous() and t.numel() == 4
 
 
-def test_longest_list_notes_python_fallback_is_keyed_by_storage_and_view():
-    """`_ops._note_longest`'s Python fallback (compiled shim absent, or GSPLAT_AMD_LIB set) keys a note by the StorageImpl's
-    address + the view (offset, numel) and keeps the noted tensor alive in its 16-entry ring, so the address cannot be handed
-    out again while the note exists and nothing depends on torch preserving a storage's Python wrapper between calls."""
-    import torch
-
-    from gsplat_amd import _ops
-
-    was = _ops._notes_compiled
-    _ops._notes_compiled = False
-    try:
-        t = torch.arange(16, dtype=torch.int32)
-        _ops._note_longest(t, 7)
-        assert _ops._lookup_longest(t) == 7 and _ops._lookup_longest(t.view(16)) == 7
-        assert _ops._lookup_longest(t[2:]) == 0 and _ops._lookup_longest(torch.arange(16, dtype=torch.int32)) == 0
-        _ops._note_longest(t, 9)  # a newer note of the same view replaces the old one
-        assert _ops._lookup_longest(t) == 9
-        for i in range(20):  # the ring holds 16 notes
-            _ops._note_longest(torch.zeros(4 + i, dtype=torch.int32), i)
-        assert len(_ops._notes_py) == 16 and _ops._lookup_longest(t) == 0
-    finally:
-        _ops._notes_py.clear()
-        _ops._notes_compiled = was
-
-
 def test_intersection_path_memory_is_per_caller_and_per_thread():
     """Which intersection kernel runs depends on retry notes (a clustered scene that was sent back is not tried again for 63
     calls). The notes belong to a caller-owned object or to the calling THREAD's private default - never to the process

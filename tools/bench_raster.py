@@ -2,8 +2,9 @@
 """Kernel-level A/B harness for the compositing kernels (run on the GPU box).
 
 Builds the bench.py c3 workload once, runs the pipeline up to the sorted tile lists, then times
-gsx_raster3d_fwd / gsx_raster3d_bwd alone with HIP events (n repeats). Select a library variant with
-GSPLAT_AMD_LIB=/path/to/libvariant.so (see gsplat_amd/_cabi.py) to compare builds in one gpurun call.
+gsx_raster3d_fwd / gsx_raster3d_bwd alone with HIP events (n repeats). Select a library variant of tools/mkvariant.sh with
+GSPLAT_AMD_LIB=/path/to/libgsplat_amd_<name>.so and GSPLAT_AMD_TORCH_LIB=/path/to/libgsplat_amd_torch_<name>.so (derived from
+the first by that naming rule when unset; see gsplat_amd/_cabi.py) to compare builds in one call.
 """
 import argparse
 import json

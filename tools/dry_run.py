@@ -4,7 +4,9 @@ The product path has no CPU fallback, so nothing can be COMPUTED here — but ev
 EXERCISED: with device pointers taken from CPU tensors and launch failures ("no ROCm-capable device") ignored, a call of
 rasterization() runs its orchestration, the op implementations, the ctypes marshalling of every C-ABI call (argument
 count / types against include/gsplat_amd.h) and the host-side checks of the entry points (GSX_REQUIRE) until something
-needs a value that only a kernel could have produced. Outputs are garbage; errors are real. Used by
+needs a value that only a kernel could have produced. The compiled op bodies (csrc/torch_ops.cpp) run on the CPU tensors
+through their CUDA-key kernel up to the point where they would touch the device; past it, the ones that would launch
+(compositing, offsets) hand out outputs of the right shape. Outputs are garbage; errors are real. Used by
 tests/test_host_dry_run.py for the empty-scene path, whose control flow does not depend on kernel results.
 
     python tools/dry_run.py            # empty 3DGS / 2DGS scenes, dense and packed, forward + backward
@@ -45,9 +47,41 @@ def install():
         mod.ptr, mod.ptr_strided, mod.call = _cabi.ptr, _cabi.ptr_strided, call
     cpu = torch.library.Library("gsplat", "IMPL", "CPU")
     for name in _ops.SCHEMAS:
-        cpu.impl(name, _ops.impl(name))
+        cpu.impl(name, _ops.impl(name) if name in _ops._impls else _compiled_on_cpu(name))
     install.keep = cpu
     return calls
+
+
+def _launch_outputs(name, a):
+    """Outputs of the compiled bodies that would launch kernels even for an empty scene (fills of the images / offsets)."""
+    if name == "intersect_offset":  # (isect_ids, I, tile_width, tile_height)
+        return torch.zeros(a[1], a[3], a[2], dtype=torch.int32)
+    means2d, colors = a[0], a[2]
+    W, H, offsets = (a[6], a[7], a[9]) if name == "rasterize_to_pixels_3dgs" else (a[8], a[9], a[11])
+    absgrad = a[12] if name == "rasterize_to_pixels_3dgs" else a[14]
+    hw = tuple(offsets.shape[:-2]) + (H, W)
+    img = lambda d: torch.empty(hw + (d,))  # noqa: E731
+    holder = torch.zeros_like(means2d) if absgrad else torch.empty(0)
+    ids = torch.empty(hw, dtype=torch.int32)
+    if name == "rasterize_to_pixels_3dgs":
+        return img(colors.shape[-1]), img(1), holder, ids
+    return img(colors.shape[-1]), img(1), img(3), img(1), img(1), holder, ids, ids.clone()
+
+
+def _compiled_on_cpu(name):
+    op = getattr(torch.ops.gsplat, name).default
+    cuda = torch._C.DispatchKeySet(torch._C.DispatchKey.CUDA)
+
+    def body(*args):
+        try:
+            return op.redispatch(cuda, *args)
+        except RuntimeError as e:  # the body's device guard / stream lookup, past its host-side checks
+            if not any(w in str(e) for w in ("ROCm-capable device", "no CPU fallback")) or name not in (
+                    "intersect_offset", "rasterize_to_pixels_3dgs", "rasterize_to_pixels_2dgs"):
+                raise
+            return _launch_outputs(name, args)
+
+    return body
 
 
 def empty_scene(fn: str, packed: bool):

@@ -24,6 +24,6 @@ run r GSX_RASTER3D_BWD=r
 # every other build of the library found next to the default one (make SUFFIX=_x EXTRA=-D...)
 for lib in $ROOT/gsplat_amd/csrc/libgsplat_amd_*.so; do
   v=$(basename $lib .so); v=${v#libgsplat_amd_}
-  [ "$v" = torch ] && continue
+  case $v in torch|torch_*) continue;; esac  # the torch library of each build (found by name from GSPLAT_AMD_LIB)
   run t_$v GSPLAT_AMD_LIB=$lib
 done
