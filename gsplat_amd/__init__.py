@@ -31,6 +31,7 @@ _LAZY = {
     # the training step around the rasterizer
     "SelectiveAdam": "optimizers", "compute_relocation": "relocation", "DefaultStrategy": "strategy",
     "MCMCStrategy": "strategy", "strategy": "strategy", "optimizers": "optimizers", "relocation": "relocation",
+    "photometric_loss": "losses", "masked_l1": "losses", "masked_ssim": "losses", "mse_loss": "losses", "losses": "losses",
     # on-disk formats
     "export_splats": "exporter", "exporter": "exporter", "PngCompression": "compression", "compression": "compression",
 }

@@ -6,6 +6,9 @@ constants C1 = 0.01^2 / C2 = 0.03^2, mean over batch, channels and pixels - the 
 convolutions (or the third-party ``fused_ssim`` CUDA extension, not available here); the window is an outer product, so this
 version runs the five maps as ONE stacked tensor through a vertical and a horizontal 11-tap pass - the same sums, 22 taps per
 output instead of 121. Plain torch ops: differentiable through autograd, runs on any device.
+
+`photometric_loss` is that whole blend with an optional mask (``masked_l1`` / ``masked_ssim``, gsplat/losses.py:328-399): one
+fused kernel pair on the GPU, the torch composition elsewhere.
 """
 from __future__ import annotations
 
@@ -101,3 +104,126 @@ def ssim_loss(img1: Tensor, img2: Tensor, window_size: int = 11) -> Tensor:
 def l1_loss(pred: Tensor, target: Tensor) -> Tensor:
     """Per-element L1 (gsplat/losses.py:48-63)."""
     return (pred - target).abs()
+
+
+def mse_loss(pred: Tensor, target: Tensor) -> Tensor:
+    """Per-element squared error (gsplat/losses.py:66-76)."""
+    return F.mse_loss(pred, target, reduction="none")
+
+
+def masked_l1(pred: Tensor, gt: Tensor, mask: Tensor) -> Tensor:
+    """Mean of ``|pred - gt|`` over the elements with ``mask != 0``; a differentiable 0 when nothing is selected
+    (gsplat/losses.py:328-357). The reference gathers the selected elements by boolean indexing, which reads their number
+    back from the device; here the selection is a ``where`` and two sums, so a training step on the GPU stays free of host
+    reads. ``mask`` broadcasts to ``pred`` (a ``[B, 1, H, W]`` mask on ``[B, C, H, W]`` images)."""
+    if pred.shape != gt.shape:
+        raise ValueError(f"masked_l1: pred shape {pred.shape} != gt shape {gt.shape}. Shapes must match.")
+    abs_diff = (pred - gt).abs()
+    selected = (mask != 0).expand_as(abs_diff)
+    count = selected.sum().clamp(min=1).to(abs_diff.dtype)  # nothing selected: 0 / 1
+    return torch.where(selected, abs_diff, torch.zeros((), dtype=abs_diff.dtype, device=abs_diff.device)).sum() / count
+
+
+def masked_ssim(pred: Tensor, gt: Tensor, mask: Tensor) -> Tensor:
+    """``ssim_loss(pred * mask, gt * mask)`` (gsplat/losses.py:360-399): both images are zeroed where the mask is, and the
+    mean still runs over the whole image, so the value scales with the mask's coverage - the reference's convention."""
+    if pred.shape != gt.shape:
+        raise ValueError(f"masked_ssim: pred shape {pred.shape} != gt shape {gt.shape}. Shapes must match.")
+    return ssim_loss(pred * mask, gt * mask)
+
+
+class _FusedPhotometric(torch.autograd.Function):
+    """lerp(l1, ssim_loss, ssim_lambda) with an optional mask on the MI355X: csrc/ssim.hip (gsx_photometric_fwd / _bwd). One
+    kernel per direction reads pred, target and the mask through their strides, a one-workgroup reduction leaves
+    (loss, l1, ssim_loss, count) in device memory, and the backward writes the whole gradient of pred. Differentiable in pred."""
+
+    calls = 0  # forwards that took the kernels (tests assert on it)
+
+    @staticmethod
+    def forward(ctx, pred: Tensor, target: Tensor, mask, ssim_lambda: float):
+        import ctypes
+
+        from . import _cabi
+
+        B, C, H, W = pred.shape
+        target = target.detach()
+        dev = pred.device
+        if mask is not None:
+            mask = mask.detach()
+            if mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)
+            elif mask.dtype not in (torch.uint8, torch.float32):
+                mask = mask.to(torch.float32)
+            mask = mask.expand(B, C, H, W)  # stride 0 along the broadcast dimensions: read in place
+        tag = 1 if mask is not None and mask.dtype == torch.uint8 else 0  # GSX_MASK_U8 / GSX_MASK_F32
+        partial = torch.empty(3 * _cabi._lib.gsx_photometric_blocks(B, C, H, W), device=dev, dtype=torch.float32)
+        record = torch.empty(4, device=dev, dtype=torch.float32)
+        need_grad = ctx.needs_input_grad[0]
+        dmaps = torch.empty((B, C, H, W, 3), device=dev, dtype=torch.float32) if need_grad else None
+        sp, st = (ctypes.c_int64 * 4)(*pred.stride()), (ctypes.c_int64 * 4)(*target.stride())
+        sm = (ctypes.c_int64 * 4)(*mask.stride()) if mask is not None else None
+        _cabi.call("gsx_photometric_fwd", _cabi.ptr_strided(pred), sp, _cabi.ptr_strided(target), st,
+                   _cabi.ptr_strided(mask) if mask is not None else None, sm, tag, B, C, H, W, float(ssim_lambda),
+                   _cabi.ptr(partial), _cabi.ptr(dmaps), _cabi.ptr(record))
+        _FusedPhotometric.calls += 1
+        ctx.save_for_backward(pred, target, mask, dmaps, record)
+        ctx.ssim_lambda, ctx.mask_tag = float(ssim_lambda), tag
+        ctx.set_materialize_grads(False)
+        loss, l1, ssim = record[0], record[1], record[2]
+        ctx.mark_non_differentiable(l1, ssim)
+        return loss, l1, ssim
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # the backward kernel is not itself differentiable
+    def backward(ctx, v_loss, _v_l1, _v_ssim):
+        import ctypes
+
+        from . import _cabi
+
+        pred, target, mask, dmaps, record = ctx.saved_tensors
+        if dmaps is None or v_loss is None:  # forward ran without a gradient request for pred / the loss was not used
+            return None, None, None, None
+        B, C, H, W = pred.shape
+        v_pred = torch.empty_like(pred)  # preserve_format: a dense permuted view (channels-last render) keeps its strides
+        sp, st, sv = ((ctypes.c_int64 * 4)(*t.stride()) for t in (pred, target, v_pred))
+        sm = (ctypes.c_int64 * 4)(*mask.stride()) if mask is not None else None
+        v_loss = v_loss.reshape(1).to(torch.float32).contiguous()  # stays on the device: the kernel multiplies by it
+        _cabi.call("gsx_photometric_bwd", _cabi.ptr_strided(pred), sp, _cabi.ptr_strided(target), st,
+                   _cabi.ptr_strided(mask) if mask is not None else None, sm, ctx.mask_tag, B, C, H, W, ctx.ssim_lambda,
+                   _cabi.ptr(dmaps), _cabi.ptr(record), _cabi.ptr(v_loss), _cabi.ptr_strided(v_pred), sv)
+        return v_pred, None, None, None
+
+
+def photometric_loss(pred: Tensor, target: Tensor, ssim_lambda: float = 0.2, mask=None, window_size: int = 11,
+                     return_parts: bool = False):
+    """The trainer's photometric loss ``lerp(l1, ssim_loss, ssim_lambda)`` (examples/simple_trainer.py:946-961) of two
+    ``[B, C, H, W]`` batches, with an optional ``mask`` broadcastable to them (``[B, 1, H, W]`` or ``[B, C, H, W]``; float,
+    bool or uint8): ``l1 = masked_l1(pred, target, mask)`` selects by ``mask != 0``, ``ssim_loss = masked_ssim(pred, target,
+    mask)`` multiplies by the mask's value (gsplat/losses.py:328-399). Without a mask: ``l1_loss(pred, target).mean()`` and
+    ``ssim_loss(pred, target)``.
+
+    float32 images on the GPU with the default window take the fused kernels - each image read once per direction, no host
+    read, one gradient image for autograd; anything else (CPU tensors, other dtypes or windows, a ``target`` that requires
+    grad, more than 65535 planes) the same composition in torch. Returns the scalar loss, or with ``return_parts`` the tuple
+    ``(loss, l1, ssim_loss)`` whose last two are detached device scalars for logging."""
+    if pred.shape != target.shape:
+        raise ValueError(f"photometric_loss: pred shape {pred.shape} != target shape {target.shape}. Shapes must match.")
+    if pred.dim() != 4:
+        raise ValueError(f"photometric_loss: expected [B, C, H, W] batches, got {tuple(pred.shape)}")
+    if not 0.0 <= float(ssim_lambda) <= 1.0:
+        raise ValueError(f"photometric_loss: ssim_lambda {ssim_lambda} outside [0, 1]")
+    if mask is not None:
+        if mask.dim() != 4 or any(m != p and m != 1 for m, p in zip(mask.shape, pred.shape)):
+            raise ValueError(f"photometric_loss: mask shape {tuple(mask.shape)} does not broadcast to {tuple(pred.shape)}")
+    if (pred.is_cuda and target.is_cuda and window_size == 11 and pred.dtype == torch.float32 and target.dtype == torch.float32
+            and not target.requires_grad and 0 < pred.shape[0] * pred.shape[1] <= 65535 and pred.numel() > 0
+            and (mask is None or (mask.device == pred.device and not mask.requires_grad))):
+        loss, l1, ssim = _FusedPhotometric.apply(pred, target, mask, float(ssim_lambda))
+    else:
+        if mask is None:
+            l1, ssim = l1_loss(pred, target).mean(), ssim_loss(pred, target, window_size)
+        else:
+            l1, ssim = masked_l1(pred, target, mask), ssim_loss(pred * mask, target * mask, window_size)  # = masked_ssim
+        loss = torch.lerp(l1, ssim, float(ssim_lambda))
+        l1, ssim = l1.detach(), ssim.detach()
+    return (loss, l1, ssim) if return_parts else loss

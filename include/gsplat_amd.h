@@ -1003,6 +1003,32 @@ int gsx_ssim_bwd(const float *img1, const int64_t *strides1, const float *img2, 
                  const int64_t *strides_v,
                  void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fused, mask-aware photometric loss of the training step: loss = lerp(l1, ssim_loss, ssim_lambda) in one kernel per direction
+ * plus one small reduction. Replaces what examples/simple_trainer.py:946-961 composes out of torch launches - l1_loss(...).mean()
+ * or, with masks, gsplat/losses.py:328-399 masked_l1 (boolean indexing: a device-to-host read) and masked_ssim (two more full
+ * images) - around the SSIM kernels above, and autograd's sum of the two gradient images.
+ *   l1        = mean of |pred - target| over the elements with mask != 0 (0 when there is none)
+ *   ssim_loss = 1 - mean over all B C H W elements of the SSIM map of (pred * mask, target * mask), window as gsx_ssim_fwd
+ * pred / target: [B, C, H, W] float32 through element strides. mask: NULL (all selected, weight 1) or a tensor addressed through
+ * its OWN element strides (0 along a broadcast dimension, e.g. the channel stride of a [B, 1, H, W] mask), elements float32
+ * (GSX_MASK_F32) or one byte, uint8 / bool (GSX_MASK_U8). ssim_lambda in [0, 1].
+ * fwd: partial_sums [3 * gsx_photometric_blocks(B, C, H, W)] is scratch (per-workgroup sums of the SSIM map, of |pred - target|
+ * and of the selected count, added in a fixed order: repeats are bit-equal); dmaps [B, C, H, W, 3] or NULL as in gsx_ssim_fwd;
+ * record [4] = (loss, l1, ssim_loss, count), device memory - nothing is read back by the host.
+ * bwd: v_pred (strides_v) = *grad_device * d loss / d pred, complete (both terms), with record the forward's; exactly 0 where
+ * the mask is 0. */
+#define GSX_MASK_F32 0
+#define GSX_MASK_U8 1
+int64_t gsx_photometric_blocks(uint32_t B, uint32_t C, uint32_t H, uint32_t W);
+int gsx_photometric_fwd(const float *pred, const int64_t *strides_pred, const float *target, const int64_t *strides_target,
+                        const void *mask, const int64_t *strides_mask, int mask_dtype, uint32_t B, uint32_t C, uint32_t H,
+                        uint32_t W, float ssim_lambda, float *partial_sums, float *dmaps, float *record, void *stream);
+int gsx_photometric_bwd(const float *pred, const int64_t *strides_pred, const float *target, const int64_t *strides_target,
+                        const void *mask, const int64_t *strides_mask, int mask_dtype, uint32_t B, uint32_t C, uint32_t H,
+                        uint32_t W, float ssim_lambda, const float *dmaps, const float *record, const float *grad_device,
+                        float *v_pred, const int64_t *strides_v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

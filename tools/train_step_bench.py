@@ -7,7 +7,7 @@ rates), SelectiveAdam (visibility-masked fused Adam) and DefaultStrategy (densif
 refinement inside the timed window).
 
 Prints one JSON object; `bench.py` embeds it as the "train_step" sub-record of the N = 1 line.
-usage: train_step_bench.py [--steps 100] [--gaussians 1000000] [--packed]"""
+usage: train_step_bench.py [--steps 100] [--gaussians 1000000] [--packed] [--fused-loss] [--mask-fraction F]"""
 import argparse
 import json
 import math
@@ -21,10 +21,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def run(steps=100, n_gaussians=1_000_000, packed=False, device=None, refine_every=None, grow_grad2d=2e-7,
-        release_cached_memory=False, refine=True, split_sh=False, ssim_lambda=0.2):
+        release_cached_memory=False, refine=True, split_sh=False, ssim_lambda=0.2, fused_loss=False, mask_fraction=0.0):
     import bench
     import gsplat_amd
-    from gsplat_amd.losses import ssim_loss
+    from gsplat_amd.losses import photometric_loss, ssim_loss
 
     dev = device or torch.device("cuda", 0)
     sc, W, H = bench.make_workload(n_gaussians, dev)
@@ -32,6 +32,11 @@ def run(steps=100, n_gaussians=1_000_000, packed=False, device=None, refine_ever
         target, _, _ = gsplat_amd.rasterization(sc["means"], sc["quats"], sc["scales"], sc["opacities"], sc["colors"],
                                                 sc["viewmats"], sc["Ks"], W, H, sh_degree=3, packed=packed)
         target = target.clamp(0, 1)
+    # mask_fraction > 0: a seeded [B, H, W] mask with that share of zeros, as the reference trainer gets from its dataset
+    # (examples/simple_trainer.py:946-949, 957-960); a generator of its own, so the model's noise below does not depend on it
+    masks = None
+    if mask_fraction > 0.0:
+        masks = (torch.rand(target.shape[:3], generator=torch.Generator().manual_seed(2)) >= mask_fraction).to(dev)
     g = torch.Generator().manual_seed(1)
     noise = lambda t, s: (t + s * torch.randn(t.shape, generator=g).to(dev))  # noqa: E731
     params = torch.nn.ParameterDict({
@@ -66,11 +71,19 @@ def run(steps=100, n_gaussians=1_000_000, packed=False, device=None, refine_ever
                                                 torch.sigmoid(params["opacities"]), colors, sc["viewmats"], sc["Ks"], W, H,
                                                 sh_degree=3, packed=packed)
         # the reference trainer's loss (examples/simple_trainer.py:951-961): lerp(L1, 1 - SSIM, ssim_lambda = 0.2)
-        l1 = (rc - target).abs().mean()
-        if ssim_lambda > 0.0:
-            loss = torch.lerp(l1, ssim_loss(rc.permute(0, 3, 1, 2), target.permute(0, 3, 1, 2)), ssim_lambda)
+        if fused_loss:  # one kernel per direction, mask read in place, no host read (gsplat_amd/losses.py: photometric_loss)
+            loss = photometric_loss(rc.permute(0, 3, 1, 2), target.permute(0, 3, 1, 2), ssim_lambda,
+                                    None if masks is None else masks[:, None])
         else:
-            loss = l1
+            if masks is None:
+                l1 = (rc - target).abs().mean()
+            else:  # the reference trainer's spelling: boolean indexing, i.e. a host read of the selected count
+                l1 = (rc[masks] - target[masks]).abs().mean()
+            if ssim_lambda > 0.0:
+                ssim_rc, ssim_target = (rc, target) if masks is None else (rc * masks[..., None], target * masks[..., None])
+                loss = torch.lerp(l1, ssim_loss(ssim_rc.permute(0, 3, 1, 2), ssim_target.permute(0, 3, 1, 2)), ssim_lambda)
+            else:
+                loss = l1
         strategy.step_pre_backward(params, opts, state, i, info)
         loss.backward()
         if packed:
@@ -105,6 +118,7 @@ def run(steps=100, n_gaussians=1_000_000, packed=False, device=None, refine_ever
                     f"packed={packed}; rasterization + lerp(L1, 1 - SSIM, {ssim_lambda}) + backward + SelectiveAdam (6 tensors) + "
                     "DefaultStrategy",
         "ssim_lambda": ssim_lambda,
+        **({"fused_loss": fused_loss, "mask_fraction": mask_fraction} if fused_loss or mask_fraction > 0.0 else {}),
         "steps": steps, "ms_per_step": round(wall / steps * 1e3, 4), "steps_per_s": round(steps / wall, 2),
         "mpixels_per_s": round(W * H * steps / wall / 1e6, 2),
         "refinement_at_step": refine_at, "refinement_step_ms": refine_ms[0] if refine_ms else None,
@@ -122,6 +136,8 @@ if __name__ == "__main__":
     ap.add_argument("--release-cached-memory", action="store_true", help="torch.cuda.empty_cache() after a refinement, as the reference does")
     ap.add_argument("--split-sh", action="store_true", help="pass colors=(sh0, shN) instead of torch.cat([sh0, shN], 1)")
     ap.add_argument("--ssim-lambda", type=float, default=0.2, help="weight of the SSIM term (the reference's default 0.2; 0 = L1 only)")
+    ap.add_argument("--fused-loss", action="store_true", help="the loss through gsplat_amd.photometric_loss (one fused kernel pair)")
+    ap.add_argument("--mask-fraction", type=float, default=0.0, help="train with a seeded [B, H, W] mask that has this share of zeros")
     a = ap.parse_args()
     print(json.dumps(run(a.steps, a.gaussians, a.packed, release_cached_memory=a.release_cached_memory, split_sh=a.split_sh,
-                         ssim_lambda=a.ssim_lambda)))
+                         ssim_lambda=a.ssim_lambda, fused_loss=a.fused_loss, mask_fraction=a.mask_fraction)))
