@@ -32,6 +32,8 @@ _LAZY = {
     "SelectiveAdam": "optimizers", "compute_relocation": "relocation", "DefaultStrategy": "strategy",
     "MCMCStrategy": "strategy", "strategy": "strategy", "optimizers": "optimizers", "relocation": "relocation",
     "photometric_loss": "losses", "masked_l1": "losses", "masked_ssim": "losses", "mse_loss": "losses", "losses": "losses",
+    # the per-image appearance correction between the render and the loss (examples/lib_bilagrid.py)
+    "BilateralGrid": "bilagrid", "bilagrid": "bilagrid", "total_variation_loss": "losses",
     # on-disk formats
     "export_splats": "exporter", "exporter": "exporter", "PngCompression": "compression", "compression": "compression",
 }

@@ -227,3 +227,62 @@ def photometric_loss(pred: Tensor, target: Tensor, ssim_lambda: float = 0.2, mas
         loss = torch.lerp(l1, ssim, float(ssim_lambda))
         l1, ssim = l1.detach(), ssim.detach()
     return (loss, l1, ssim) if return_parts else loss
+
+
+def total_variation_torch(x: Tensor) -> Tensor:
+    """`total_variation_loss` composed of torch calls (any device, dtype and number of spatial axes)."""
+    if x.dim() < 3:
+        raise ValueError(f"total_variation_loss: expected [B, C, d1, ...], got {tuple(x.shape)}")
+    tv = x.new_zeros(())
+    for axis in range(2, x.dim()):
+        n = x.shape[axis] - 1
+        if n <= 0:  # nothing to difference along this axis
+            continue
+        d = x.narrow(axis, 1, n) - x.narrow(axis, 0, n)
+        tv = tv + d.pow(2).sum() / max(float(d.numel() // max(d.shape[0], 1)), 1.0)
+    return tv / x.shape[0]
+
+
+class _FusedTotalVariation(torch.autograd.Function):
+    """Total variation of a [B, C, D1, D2, D3] tensor on the MI355X: csrc/bilagrid.hip (gsx_tv_fwd / gsx_tv_bwd). Per-workgroup
+    sums added by one workgroup in a fixed order; the value stays in device memory and the backward reads its incoming
+    gradient there."""
+
+    calls = 0  # forwards that took the kernels (tests assert on it)
+
+    @staticmethod
+    def forward(ctx, x: Tensor):
+        from . import _cabi
+
+        xc = x.contiguous()
+        partial = torch.empty(_cabi._lib.gsx_tv_blocks(*xc.shape), device=x.device, dtype=torch.float32)
+        out = torch.empty(1, device=x.device, dtype=torch.float32)
+        _cabi.call("gsx_tv_fwd", _cabi.ptr(xc), *xc.shape, _cabi.ptr(partial), _cabi.ptr(out))
+        _FusedTotalVariation.calls += 1
+        ctx.save_for_backward(xc)
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # the backward kernel is not itself differentiable
+    def backward(ctx, v_loss: Tensor):
+        from . import _cabi
+
+        (xc,) = ctx.saved_tensors
+        v_x = torch.empty_like(xc)
+        v_loss = v_loss.reshape(1).to(torch.float32).contiguous()  # stays on the device: the kernel multiplies by it
+        _cabi.call("gsx_tv_bwd", _cabi.ptr(xc), *xc.shape, _cabi.ptr(v_loss), _cabi.ptr(v_x))
+        return v_x
+
+
+def total_variation_loss(x: Tensor) -> Tensor:
+    """Total variation of ``x [B, C, d1, ...]`` (gsplat/losses.py:642-667; the regulariser of the bilateral grids,
+    examples/simple_trainer.py:981-984): for every spatial axis the sum of squared forward differences divided by the element
+    count of the differenced tensor without its batch axis (at least 1), summed over the axes, divided by ``B``.
+
+    A float32 5-D tensor on the GPU (a stack of bilateral grids ``[N, 12, L, Hg, Wg]``) takes the fused kernels: one pass and a
+    one-workgroup reduction forward, one pass backward, no host read. Anything else the same sums in torch."""
+    if x.dim() < 3:
+        raise ValueError(f"total_variation_loss: expected [B, C, d1, ...], got {tuple(x.shape)}")
+    if x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and 0 < x.numel() < 2 ** 31:
+        return _FusedTotalVariation.apply(x)
+    return total_variation_torch(x)

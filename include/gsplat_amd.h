@@ -1029,6 +1029,43 @@ int gsx_photometric_bwd(const float *pred, const int64_t *strides_pred, const fl
                         uint32_t W, float ssim_lambda, const float *dmaps, const float *record, const float *grad_device,
                         float *v_pred, const int64_t *strides_v, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Bilateral-grid appearance model between the render and the loss (examples/simple_trainer.py with
+ * post_processing="bilateral_grid"; examples/lib_bilagrid.py:110-295): every pixel slices a 3 x 4 affine colour matrix out of
+ * grid grid_idx[image] of grids [N, 12, L, Hg, Wg] (float32, contiguous; the 12 channels are the matrix, row-major) and applies
+ * it: rgb_out = A[:, :3] rgb + A[:, 3]. Sampling is F.grid_sample's trilinear, align_corners=True, padding_mode="border", at
+ * (ix, iy, iz) = (u (Wg - 1), v (Hg - 1), gray (L - 1)) with gray = 0.299 r + 0.587 g + 0.114 b of the INPUT colour; an index
+ * clamped to its axis passes no gradient.
+ * rgb: [I, H, W, 3] through element strides (i, h, w, c) - a [..., :3] view of a wider render is read in place. xy: NULL =
+ * pixel centres (u, v) = ((x + 0.5) / W, (y + 0.5) / H), else [I, H, W, 2] through its own strides. grid_idx: [I] int64 in
+ * device memory, read by the kernels; an index outside [0, N) gives NaN colours and no gradient, never an access outside grids.
+ * fwd: rgb_out [I, H, W, 3] contiguous; affine_mats [I, H, W, 12] contiguous or NULL (not written).
+ * H, W < 2^22.
+ * bwd: v_rgb_out through strides_v; v_rgb [I, H, W, 3] contiguous, every element written (the gradient through the affine
+ * product and through the guidance iz); v_grids [N, 12, L, Hg, Wg] is ADDED to (the caller zeroes it). Either may be NULL: that
+ * gradient is not wanted and its work is skipped. With xy == NULL the sum
+ * over a grid cell's pixels is taken in LDS and one atomic per touched grid element and workgroup reaches memory; with an xy
+ * tensor (or L > 170) every (pixel, corner, channel) is one global atomic add. Either way v_grids is a float atomic sum: equal
+ * to a few ulp between runs, not bit for bit. No gradient is produced for xy. */
+int gsx_bilagrid_slice_fwd(const float *grids, uint32_t N, uint32_t L, uint32_t Hg, uint32_t Wg, const float *rgb,
+                           const int64_t *strides_rgb, const float *xy, const int64_t *strides_xy, const int64_t *grid_idx,
+                           uint32_t I, uint32_t H, uint32_t W, float *rgb_out, float *affine_mats, void *stream);
+int gsx_bilagrid_slice_bwd(const float *grids, uint32_t N, uint32_t L, uint32_t Hg, uint32_t Wg, const float *rgb,
+                           const int64_t *strides_rgb, const float *xy, const int64_t *strides_xy, const int64_t *grid_idx,
+                           uint32_t I, uint32_t H, uint32_t W, const float *v_rgb_out, const int64_t *strides_v, float *v_rgb,
+                           float *v_grids, void *stream);
+
+/* Total variation of x [B, C, D1, D2, D3] (float32, contiguous; gsplat/losses.py:642-667): for each of the three spatial axes
+ * the sum of squared forward differences divided by the element count of the differenced tensor without its batch axis (at
+ * least 1), summed over the axes, divided by B.
+ * fwd: partial_sums [gsx_tv_blocks(...)] is scratch (per-workgroup sums, added in a fixed order in double: repeats are
+ * bit-equal); loss [1] stays in device memory. bwd: v_x (contiguous, every element written) = *grad_device * d loss / d x. */
+int64_t gsx_tv_blocks(uint32_t B, uint32_t C, uint32_t D1, uint32_t D2, uint32_t D3);
+int gsx_tv_fwd(const float *x, uint32_t B, uint32_t C, uint32_t D1, uint32_t D2, uint32_t D3, float *partial_sums, float *loss,
+               void *stream);
+int gsx_tv_bwd(const float *x, uint32_t B, uint32_t C, uint32_t D1, uint32_t D2, uint32_t D3, const float *grad_device,
+               float *v_x, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
