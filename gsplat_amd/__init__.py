@@ -34,6 +34,8 @@ _LAZY = {
     "photometric_loss": "losses", "masked_l1": "losses", "masked_ssim": "losses", "mse_loss": "losses", "losses": "losses",
     # the per-image appearance correction between the render and the loss (examples/lib_bilagrid.py)
     "BilateralGrid": "bilagrid", "bilagrid": "bilagrid", "total_variation_loss": "losses",
+    # the per-Gaussian appearance MLP of the trainer's app_opt path (examples/utils.py: AppearanceOptModule)
+    "AppearanceOptModule": "appearance", "appearance": "appearance",
     # on-disk formats
     "export_splats": "exporter", "exporter": "exporter", "PngCompression": "compression", "compression": "compression",
 }

@@ -1066,6 +1066,32 @@ int gsx_tv_fwd(const float *x, uint32_t B, uint32_t C, uint32_t D1, uint32_t D2,
 int gsx_tv_bwd(const float *x, uint32_t B, uint32_t C, uint32_t D1, uint32_t D2, uint32_t D3, const float *grad_device,
                float *v_x, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-Gaussian appearance MLP of the training step (examples/simple_trainer.py with app_opt=True; examples/utils.py:66-129):
+ * colors[c, n] = W3 relu(W2 relu(W1 x + b1) + b2) + b3 with x = [embed[c] (E) | features[n] (32) | the 16 SH bases of
+ * normalize(dirs[c, n])], bases beyond (sh_degree + 1)^2 zero, 64 hidden units, E = embed_dim in {0, 16}. All float32.
+ * features [N, 32] contiguous, 16-byte aligned; dirs [C, N, 3] through element strides (c, n, xyz); W1 [64, E + 48], W2
+ * [64, 64], W3 [3, 64], b2 [64], b3 [3] contiguous; bias1 [C, 64] = b1 + W1[:, :E] embed[c] (the embedding's part of layer 1,
+ * constant per camera, formed by the caller; b1 repeated where there is no embedding). 0 < N < 2^31, 0 < C < 2^16.
+ * fwd: colors [C, N, 3] contiguous, every element written.
+ * bwd (recomputes the forward): v_colors [C, N, 3] contiguous; embeds [C, 16] (the embeddings behind bias1) or NULL = zero or
+ * none; workspace [gsx_appearance_bwd_workspace_floats(N, C)] is scratch. Written, every element: v_features [N, 32] (summed
+ * over the cameras in order); v_dirs [C, N, 3] contiguous or NULL (not wanted); v_W1x [64, 64], the gradient of W1 with its
+ * columns in the order [features 32 | SH 16 | embedding 16] (the last 16 are zero without embeds); v_W2 [64, 64]; v_small
+ * [260 + 64 C] = v_b2 [64] | v_W3 [3, 64] | v_b3 [3] | 0 | s [C, 64], s[c] the sum over n of the gradient at layer 1's
+ * pre-activation, from which the caller forms v_b1 = sum_c s[c] and v_embed[c] = W1[:, :E]^T s[c].
+ * No float atomics: per-wave and per-workgroup partial sums added in a fixed order, so repeats are bit-equal. */
+int gsx_appearance_fwd(const float *features, const float *dirs, const int64_t *strides_dirs, const float *bias1,
+                       const float *W1, uint32_t embed_dim, const float *W2, const float *b2, const float *W3, const float *b3,
+                       int64_t N, uint32_t C, uint32_t sh_degree, float *colors, void *stream);
+int64_t gsx_appearance_bwd_blocks(int64_t N);
+int64_t gsx_appearance_bwd_workspace_floats(int64_t N, uint32_t C);
+int gsx_appearance_bwd(const float *features, const float *dirs, const int64_t *strides_dirs, const float *embeds,
+                       const float *bias1, const float *W1, uint32_t embed_dim, const float *W2, const float *b2,
+                       const float *W3, const float *b3, int64_t N, uint32_t C, uint32_t sh_degree, const float *v_colors,
+                       float *workspace, float *v_features, float *v_dirs, float *v_W1x, float *v_W2, float *v_small,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
