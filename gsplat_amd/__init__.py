@@ -36,6 +36,8 @@ _LAZY = {
     "BilateralGrid": "bilagrid", "bilagrid": "bilagrid", "total_variation_loss": "losses",
     # the per-Gaussian appearance MLP of the trainer's app_opt path (examples/utils.py: AppearanceOptModule)
     "AppearanceOptModule": "appearance", "appearance": "appearance",
+    # before step 0: the nearest-neighbour scale initialisation (gsplat/init_utils.py, examples/utils.py: knn)
+    "knn": "init_utils", "knn_scale_init": "init_utils", "init_utils": "init_utils",
     # on-disk formats
     "export_splats": "exporter", "exporter": "exporter", "PngCompression": "compression", "compression": "compression",
 }

@@ -270,6 +270,10 @@ def appearance_bwd_workspace_floats(n: int, n_cameras: int) -> int:
     return int(_lib.gsx_appearance_bwd_workspace_floats(n, n_cameras))
 
 
+def knn_workspace_bytes(n: int, k: int) -> int:
+    return int(_lib.gsx_knn_workspace_bytes(n, k))
+
+
 def tile_sort_supported(n_images: int, tile_w: int, tile_h: int) -> bool:
     return bool(_lib.gsx_isect_tile_sort_supported(n_images, tile_w, tile_h))
 

@@ -1092,6 +1092,28 @@ int gsx_appearance_bwd(const float *features, const float *dirs, const int64_t *
                        float *workspace, float *v_features, float *v_dirs, float *v_W1x, float *v_W2, float *v_small,
                        void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact k-nearest-neighbour search of a point cloud against itself, the kernel of the scale initialisation every reference
+ * trainer starts with: gsplat/init_utils.py:145 knn_scale_init (chunked torch.cdist + topk, O(N^2)) and examples/utils.py:156
+ * knn (scikit-learn NearestNeighbors(n_neighbors=K).fit(x).kneighbors(x) on the host; simple_trainer.py:321).
+ * x [N, 3] float32 contiguous, 0 < N < 2^31 - 1. For every row the K smallest Euclidean distances to the rows of x, itself
+ * included (column 0 is 0), ascending, from coordinate differences: sqrt((dx dx + dy dy) + dz dz). 1 <= K <= min(16, N).
+ * Two calls with a sort of `keys` between them (the keys are distinct: any ascending int64 sort serves):
+ *   gsx_knn_bin     bins the finite points into a uniform grid chosen on the device; writes keys [N] int64 (cell << 32 | row).
+ *   gsx_knn_search  sorted_keys [N] ascending; dist [N, K]; idx [N, K] int64 or NULL (not wanted). Ring walk over the grid,
+ *                   ring_cap <= 1024 rings per query, then one workgroup per query still open, scanning all points.
+ * workspace [gsx_knn_workspace_bytes(N, K)] bytes, 256-byte aligned, the same buffer for both calls (its size depends on N
+ * alone; 0 for an N outside the range). Its first 64 bytes after gsx_knn_search: float bmin[3], scale[3], cell[3]; int32
+ * dims[3]; uint32 number of rows that took the all-points scan; uint32 cell count.
+ * A row of x with a NaN or infinite coordinate is nobody's neighbour and its own row is NaN / -1. Fewer than K neighbours at a
+ * distance representable in float32: the rest of the row is inf / -1. Among equal distances which row is reported is
+ * unspecified; the distances themselves are exact, bit-equal between runs and independent of the order of the rows.
+ * No host read of device data, no float atomics. */
+int64_t gsx_knn_workspace_bytes(int64_t N, uint32_t K);
+int gsx_knn_bin(const float *x, int64_t N, void *workspace, int64_t *keys, void *stream);
+int gsx_knn_search(const float *x, const int64_t *sorted_keys, int64_t N, uint32_t K, uint32_t ring_cap, void *workspace,
+                   float *dist, int64_t *idx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
