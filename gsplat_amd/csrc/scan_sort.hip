@@ -130,7 +130,9 @@ int run_scan_i32_exclusive(const int32_t *in, int64_t n, int32_t *out, void *ws,
 int64_t scan_workspace_bytes_for(int64_t n) { return scan_ws_bytes(n); }
 
 // ------------------------------------------------------------------------------------------
-// radix sort of (int64 key, int32 value) pairs, 8 bits per pass.
+// radix sort of (int64 key, int32 value) pairs, 8 bits per pass. The order is that of the key bits [0, end_bit) read as an
+// UNSIGNED integer (end_bit 64: bit 63 set sorts last); bits at or above end_bit are carried along and decide nothing - the
+// last pass masks its digit to the end_bit - shift bits that remain.
 // ------------------------------------------------------------------------------------------
 constexpr int kSortThreads = 256;
 constexpr int kSortRounds  = 16;                          // keys per lane
@@ -140,7 +142,7 @@ constexpr int kRadix       = 256;
 
 // per-workgroup digit histogram, stored digit-major: hist[d * n_chunks + chunk]
 __global__ void __launch_bounds__(kSortThreads)
-sort_hist_kernel(const uint64_t *keys, int64_t n, int shift, int64_t n_chunks, int32_t *hist)
+sort_hist_kernel(const uint64_t *keys, int64_t n, int shift, uint32_t digit_mask, int64_t n_chunks, int32_t *hist)
 {
     __shared__ int32_t s_hist[kRadix];
     s_hist[threadIdx.x] = 0;
@@ -149,7 +151,7 @@ sort_hist_kernel(const uint64_t *keys, int64_t n, int shift, int64_t n_chunks, i
 #pragma unroll
     for (int i = 0; i < kSortRounds; ++i) {
         const int64_t idx = base + (int64_t)i * kSortThreads + threadIdx.x;
-        if (idx < n) atomicAdd(&s_hist[(int)((keys[idx] >> shift) & 0xFFu)], 1);
+        if (idx < n) atomicAdd(&s_hist[(int)((keys[idx] >> shift) & digit_mask)], 1);
     }
     __syncthreads();
     hist[(int64_t)threadIdx.x * n_chunks + blockIdx.x] = s_hist[threadIdx.x];
@@ -157,7 +159,8 @@ sort_hist_kernel(const uint64_t *keys, int64_t n, int shift, int64_t n_chunks, i
 
 __global__ void __launch_bounds__(kSortThreads)
 sort_scatter_kernel(const uint64_t *keys_in, const int32_t *vals_in, uint64_t *keys_out, int32_t *vals_out,
-                    int64_t n, int shift, int64_t n_chunks, const int32_t *hist_scanned /* exclusive, digit-major */)
+                    int64_t n, int shift, uint32_t digit_mask, int64_t n_chunks,
+                    const int32_t *hist_scanned /* exclusive, digit-major */)
 {
     __shared__ int32_t s_cnt[4][kRadix];  // per-wave running digit counts
     __shared__ int32_t s_base[4][kRadix]; // global base + exclusive prefix over waves
@@ -176,8 +179,9 @@ sort_scatter_kernel(const uint64_t *keys_in, const int32_t *vals_in, uint64_t *k
         const int64_t idx = wave_base + (int64_t)r * 64 + lane;
         const bool live   = idx < n;
         key[r]            = live ? keys_in[idx] : ~0ull;
-        const int d       = (int)((key[r] >> shift) & 0xFFu);
-        // lanes of this wave holding the same digit (dead lanes match nobody that is live)
+        const int d       = (int)((key[r] >> shift) & digit_mask);
+        // lanes of this wave holding the same digit (the ballot of `live` seeds the set: a dead lane, whose pad key reads
+        // as the digit `digit_mask`, is no peer of a live lane whatever the mask)
         uint64_t peers = __builtin_amdgcn_ballot_w64(live);
 #pragma unroll
         for (int bit = 0; bit < 8; ++bit) {
@@ -211,7 +215,7 @@ sort_scatter_kernel(const uint64_t *keys_in, const int32_t *vals_in, uint64_t *k
     for (int r = 0; r < kSortRounds; ++r) {
         const int64_t idx = wave_base + (int64_t)r * 64 + lane;
         if (idx < n) {
-            const int d       = (int)((key[r] >> shift) & 0xFFu);
+            const int d       = (int)((key[r] >> shift) & digit_mask);
             const int64_t dst = (int64_t)s_base[wave][d] + rank[r];
             keys_out[dst]     = key[r];
             vals_out[dst]     = vals_in[idx];
@@ -268,11 +272,15 @@ extern "C" int gsx_sort_pairs(int64_t *keys, int32_t *vals, int64_t *keys_alt, i
     const int passes = (end_bit + 7) / 8;
     for (int p = 0; p < passes; ++p) {
         const int shift = 8 * p;
-        sort_hist_kernel<<<dim3((uint32_t)n_chunks), dim3(kSortThreads), 0, s>>>(k_in, n, shift, n_chunks, hist);
+        // the last pass ranks by the bits below end_bit only: a key bit at or above end_bit never moves a pair
+        const int bits           = end_bit - shift < 8 ? end_bit - shift : 8;
+        const uint32_t digit_mask = (1u << bits) - 1u;
+        sort_hist_kernel<<<dim3((uint32_t)n_chunks), dim3(kSortThreads), 0, s>>>(k_in, n, shift, digit_mask, n_chunks,
+                                                                               hist);
         int rc = run_scan<int32_t, false>(hist, n_hist, hist_scanned, scan_ws, scan_ws_b, s);
         if (rc != GSX_OK) return rc;
         sort_scatter_kernel<<<dim3((uint32_t)n_chunks), dim3(kSortThreads), 0, s>>>(k_in, v_in, k_out, v_out, n, shift,
-                                                                                  n_chunks, hist_scanned);
+                                                                                  digit_mask, n_chunks, hist_scanned);
         rc = check_launch("sort_scatter");
         if (rc != GSX_OK) return rc;
         uint64_t *tk = k_in; k_in = k_out; k_out = tk;

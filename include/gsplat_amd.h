@@ -501,7 +501,9 @@ int64_t gsx_scan_workspace_bytes(int64_t n);
 int gsx_scan_i32(const int32_t *in, int64_t n, int64_t *out_inclusive, void *workspace, int64_t workspace_bytes,
                  void *stream);
 int64_t gsx_sort_pairs_workspace_bytes(int64_t n);
-/* Sorts (keys, vals) by key bits [0,end_bit). keys_alt/vals_alt are ping-pong buffers of the same size.
+/* Stable sort of (keys, vals) by key bits [0,end_bit) read as an UNSIGNED integer, ascending (end_bit 64: a key with bit 63
+ * set sorts last). Bits at or above end_bit are carried along and never move a pair; end_bit 0 touches no buffer.
+ * keys_alt/vals_alt are ping-pong buffers of the same size.
  * On return *result_in_alt tells whether the sorted data is in the alt buffers (1) or the primary (0). */
 int gsx_sort_pairs(int64_t *keys, int32_t *vals, int64_t *keys_alt, int32_t *vals_alt, int64_t n, int end_bit,
                    void *workspace, int64_t workspace_bytes, int *result_in_alt, void *stream);
