@@ -274,6 +274,10 @@ def knn_workspace_bytes(n: int, k: int) -> int:
     return int(_lib.gsx_knn_workspace_bytes(n, k))
 
 
+def kmeans_workspace_bytes(n: int, d: int, k: int) -> int:
+    return int(_lib.gsx_kmeans_workspace_bytes(n, d, k))
+
+
 def tile_sort_supported(n_images: int, tile_w: int, tile_h: int) -> bool:
     return bool(_lib.gsx_isect_tile_sort_supported(n_images, tile_w, tile_h))
 

@@ -10,7 +10,7 @@ directory written here decompresses with the reference and the other way round. 
 
 What this module does not take from the reference are its three third-party dependencies, none of which is in this image:
 ``imageio`` -> the PNG codec in ``_png.py``; ``torchpq.clustering.KMeans`` -> ``kmeans_l1`` below (Lloyd's iteration with
-L1 assignment, chunked); ``plas`` -> see ``sort.py``.
+L1 assignment: the kernels of csrc/kmeans.hip on the GPU, a chunked torch composition elsewhere); ``plas`` -> see ``sort.py``.
 """
 from __future__ import annotations
 
@@ -123,12 +123,83 @@ class _Npz:
         return torch.from_numpy(arr).reshape(meta["shape"]).to(getattr(torch, meta["dtype"]))
 
 
-def kmeans_l1(x: Tensor, n_clusters: int, n_iters: int = 10, seed: int = 0, max_chunk_elems: int = 1 << 27,
-              verbose: bool = False) -> Tuple[Tensor, Tensor]:
-    """Lloyd's iteration with Manhattan-distance assignment (what the reference asks of torchpq's KMeans,
-    ``distance="manhattan"``; png_compression.py:348-351). x [N, D] -> (centroids [K, D], labels int64 [N]),
-    K = min(n_clusters, N). Initial centroids: K distinct rows drawn with `seed`; a cluster that loses all its members
-    keeps its centroid. The assignment is evaluated in row chunks of at most `max_chunk_elems` / (K D) rows."""
+_KMEANS_FUSED_MAX_D = 128  # csrc/kmeans.hip
+
+
+def _kmeans_fused_config_ok(device_type: str, dtype: torch.dtype, shape) -> bool:
+    """The configuration csrc/kmeans.hip serves: float32 rows [N, D] on a ROCm device, 1 <= D <= 128, N < 2^31 - 1."""
+    return (device_type == "cuda" and dtype == torch.float32 and len(shape) == 2 and 1 <= shape[1] <= _KMEANS_FUSED_MAX_D
+            and shape[0] < 2 ** 31 - 1)
+
+
+def _kmeans_fused_ok(x: Tensor) -> bool:
+    return _kmeans_fused_config_ok(x.device.type, x.dtype, tuple(x.shape))
+
+
+def _assign_fused(x: Tensor, centroids: Tensor, want_best: bool) -> Tuple[Tensor, Tensor]:
+    """gsx_kmeans_assign_l1: int32 labels [N] and, when wanted, the float32 distances [N]."""
+    from .. import _cabi
+
+    n, d = x.shape
+    with torch.cuda.device(x.device):
+        labels = torch.empty(n, dtype=torch.int32, device=x.device)
+        best = torch.empty(n, dtype=torch.float32, device=x.device) if want_best else None
+        if n:
+            _cabi.call("gsx_kmeans_assign_l1", _cabi.ptr(x), n, d, _cabi.ptr(centroids), centroids.shape[0], _cabi.ptr(labels),
+                       _cabi.ptr(best))
+    return labels, best
+
+
+def _update_fused(x: Tensor, labels: Tensor, centroids: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """gsx_kmeans_update: (new centroids [K, D], counts int32 [K], largest centroid move float32 [1]) from int32 labels: one
+    sort of the distinct keys ``label << 32 | row``, then fixed-order sums (no float atomics: bit-equal between runs). A
+    cluster without rows keeps its centroid."""
+    from .. import _cabi
+
+    n, d = x.shape
+    k = centroids.shape[0]
+    with torch.cuda.device(x.device):
+        keys = (labels.to(torch.int64) << 32) | torch.arange(n, dtype=torch.int64, device=x.device)
+        keys = torch.sort(keys).values
+        new = torch.empty_like(centroids)
+        counts = torch.empty(k, dtype=torch.int32, device=x.device)
+        shift = torch.empty(1, dtype=torch.float32, device=x.device)
+        work = torch.empty(_cabi.kmeans_workspace_bytes(n, d, k), dtype=torch.uint8, device=x.device)
+        _cabi.call("gsx_kmeans_update", _cabi.ptr(x), n, d, _cabi.ptr(labels), _cabi.ptr(keys), k, _cabi.ptr(centroids),
+                   _cabi.ptr(new), _cabi.ptr(counts), _cabi.ptr(shift), _cabi.ptr(work))
+    return new, counts, shift
+
+
+def kmeans_assign_l1(x: Tensor, centroids: Tensor, return_distance: bool = False):
+    """Nearest centroid by Manhattan distance: ``labels`` int64 [N], with ``return_distance`` also the distances [N].
+
+    The distance of a pair is defined exactly: one accumulator of x's dtype that starts at 0 and takes
+    ``acc = acc + |x[i, d] - c[j, d]|`` for d = 0 .. D - 1 in ascending order; the label is the lowest j among the minimal
+    distances. float32 CUDA rows with D <= 128 take the kernel of csrc/kmeans.hip (no row-by-centroid matrix); everything else
+    evaluates the same definition with tensor operations, a loop over d on any device and dtype - the same bits where both
+    apply. A row whose distances are all NaN or +inf (a non-finite coordinate) gets label 0 and distance +inf."""
+    if x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1] or centroids.shape[0] < 1:
+        raise ValueError(f"kmeans_assign_l1: x {tuple(x.shape)} against centroids {tuple(centroids.shape)}")
+    if _kmeans_fused_ok(x) and _kmeans_fused_ok(centroids) and centroids.device == x.device:
+        labels, best = _assign_fused(x.detach().contiguous(), centroids.detach().contiguous(), return_distance)
+        labels = labels.to(torch.int64)
+        return (labels, best) if return_distance else labels
+    centroids = centroids.to(x.dtype)
+    acc = torch.zeros((x.shape[0], centroids.shape[0]), dtype=x.dtype, device=x.device)
+    for d in range(x.shape[1]):
+        acc = acc + (x[:, d, None] - centroids[None, :, d]).abs()
+    acc = torch.where(acc < float("inf"), acc, torch.full_like(acc, float("inf")))  # NaN -> +inf: never the minimum
+    best = acc.min(dim=1).values
+    k = centroids.shape[0]
+    cols = torch.arange(k, device=x.device).expand_as(acc)
+    labels = torch.where(acc == best[:, None], cols, torch.full_like(cols, k)).min(dim=1).values  # the lowest minimal index
+    return (labels, best) if return_distance else labels
+
+
+def kmeans_l1_torch(x: Tensor, n_clusters: int, n_iters: int = 10, seed: int = 0, max_chunk_elems: int = 1 << 27,
+                    verbose: bool = False) -> Tuple[Tensor, Tensor]:
+    """`kmeans_l1` composed of tensor operations on any device and dtype: ``torch.cdist(p=1).argmin`` in row chunks of at most
+    `max_chunk_elems` / (K D) rows, ``index_add_`` for the sums."""
     n, d = x.shape
     k = min(n_clusters, n)
     gen = torch.Generator(device="cpu").manual_seed(seed)
@@ -150,6 +221,40 @@ def kmeans_l1(x: Tensor, n_clusters: int, n_iters: int = 10, seed: int = 0, max_
     for lo in range(0, n, chunk):  # labels of the final centroids
         labels[lo:lo + chunk] = torch.cdist(x[lo:lo + chunk], centroids, p=1).argmin(dim=1)
     return centroids, labels
+
+
+def _kmeans_l1_fused(x: Tensor, n_clusters: int, n_iters: int, seed: int, verbose: bool) -> Tuple[Tensor, Tensor]:
+    n = x.shape[0]
+    k = min(n_clusters, n)
+    x = x.detach().contiguous()
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    centroids = x[torch.randperm(n, generator=gen)[:k].to(x.device)].clone()
+    for it in range(max(1, n_iters)):
+        labels, _ = _assign_fused(x, centroids, False)
+        centroids, _, shift_dev = _update_fused(x, labels, centroids)
+        shift = float(shift_dev)  # the one value read back per iteration
+        if verbose:
+            print(f"kmeans_l1: iteration {it + 1}/{n_iters}, largest centroid move {shift:.3e}")
+        if shift == 0.0:
+            break
+    labels, _ = _assign_fused(x, centroids, False)  # labels of the final centroids
+    return centroids, labels.to(torch.int64)
+
+
+def kmeans_l1(x: Tensor, n_clusters: int, n_iters: int = 10, seed: int = 0, max_chunk_elems: int = 1 << 27,
+              verbose: bool = False) -> Tuple[Tensor, Tensor]:
+    """Lloyd's iteration with Manhattan-distance assignment (what the reference asks of torchpq's KMeans,
+    ``distance="manhattan"``; png_compression.py:348-351). x [N, D] -> (centroids [K, D], labels int64 [N]),
+    K = min(n_clusters, N). Initial centroids: K distinct rows drawn with `seed`; a cluster that loses all its members
+    keeps its centroid; the iteration stops early when no centroid moves.
+
+    float32 CUDA rows with D <= 128 (`_kmeans_fused_ok`) take the kernels of csrc/kmeans.hip: the assignment of
+    `kmeans_assign_l1`, and means summed in a fixed order after one sort of (label, row) keys - no row-by-centroid matrix, no
+    float atomics, the same bits on every run. Everything else (CPU, float64, D > 128) is `kmeans_l1_torch`, where the
+    assignment is evaluated in row chunks of at most `max_chunk_elems` / (K D) rows."""
+    if x.shape[0] > 0 and _kmeans_fused_ok(x):
+        return _kmeans_l1_fused(x, n_clusters, n_iters, seed, verbose)
+    return kmeans_l1_torch(x, n_clusters, n_iters, seed, max_chunk_elems, verbose)
 
 
 class _KMeans:

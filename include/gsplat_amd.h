@@ -1116,6 +1116,32 @@ int gsx_knn_bin(const float *x, int64_t N, void *workspace, int64_t *keys, void 
 int gsx_knn_search(const float *x, const int64_t *sorted_keys, int64_t N, uint32_t K, uint32_t ring_cap, void *workspace,
                    float *dist, int64_t *idx, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Lloyd's iteration with Manhattan-distance assignment: the SH codebook of PngCompression (the reference hands it to torchpq's
+ * KMeans, distance="manhattan": gsplat/compression/png_compression.py:348-351). float32, x [N, D] and centroids [K, D]
+ * contiguous, 1 <= D <= 128, K >= 1, N < 2^31 - 1.
+ *   gsx_kmeans_assign_l1  The distance of a pair is one float32 accumulator that starts at 0 and takes
+ *                         acc = acc + |x[i, d] - c[j, d]| for d = 0 .. D - 1 in ascending order. labels[i] (int32) = the lowest j
+ *                         among the minimal distances (a strict < while j goes up); best [N] (or NULL: not wanted) = that
+ *                         distance. A pair's value does not depend on the tiling, so both are bit-reproducible and equal to a
+ *                         plain loop's. No row-by-centroid matrix is formed. A row whose distances are all NaN or +inf (a NaN or
+ *                         infinite coordinate) gets label 0 and best = +inf: never a fault, never a label outside [0, K).
+ *                         N = 0 is a no-op.
+ *   gsx_kmeans_update     sorted_keys [N] int64 = labels[i] << 32 | i, sorted ascending by the caller (the keys are distinct:
+ *                         any ascending sort serves); labels [N] itself is not read and may be NULL. centroids_out[k] = the mean
+ *                         of the rows of cluster k, added in a fixed order: runs of 32 consecutive sorted rows first, then a
+ *                         cluster's run sums in eight interleaved chains, then those eight in order - so the depth of the
+ *                         additions is n_k / 256 + 40 for a cluster of n_k rows, and all rows in one cluster is a legitimate
+ *                         input. A cluster without rows keeps centroids_in[k] bit for bit. counts [K] int32 = rows per cluster;
+ *                         shift [1] = max |centroids_out - centroids_in|, written on the device. centroids_out must not alias
+ *                         centroids_in. No float atomics: two runs on the same input give the same bits. N >= 1.
+ * workspace [gsx_kmeans_workspace_bytes(N, D, K)] bytes, 256-byte aligned (0 for arguments outside the range). */
+int gsx_kmeans_assign_l1(const float *x, int64_t N, uint32_t D, const float *centroids, int64_t K, int32_t *labels, float *best,
+                         void *stream);
+int64_t gsx_kmeans_workspace_bytes(int64_t N, uint32_t D, int64_t K);
+int gsx_kmeans_update(const float *x, int64_t N, uint32_t D, const int32_t *labels, const int64_t *sorted_keys, int64_t K,
+                      const float *centroids_in, float *centroids_out, int32_t *counts, float *shift, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
