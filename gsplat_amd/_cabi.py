@@ -197,12 +197,12 @@ _torch_lib = None
 
 
 def torch_lib() -> ctypes.CDLL:
-    """libgsplat_amd_torch.so (csrc/torch_ops.cpp; gsplat_amd._ops loads it at import): the long-tile hint of its compositing
+    """libgsplat_amd_torch.so (csrc/torch_ops.cpp; gsplat_amd._ops loads it at import): the segment length of its compositing
     body, and the event-pair hooks of its op bodies, which call the C-ABI without passing through call() below."""
     global _torch_lib
     if _torch_lib is None:
         lib = ctypes.CDLL(torch_lib_path())
-        lib.gsx_torch_set_long_tile_hint.argtypes, lib.gsx_torch_set_long_tile_hint.restype = [ctypes.c_int64], None
+        lib.gsx_torch_seg_len.argtypes, lib.gsx_torch_seg_len.restype = [], ctypes.c_int64
         lib.gsx_torch_profile_begin.argtypes, lib.gsx_torch_profile_begin.restype = [ctypes.c_char_p], None
         lib.gsx_torch_profile_end.restype = ctypes.c_char_p
         _torch_lib = lib
@@ -290,24 +290,6 @@ def isect_fused_supported(n_images: int, tile_w: int, tile_h: int, packed: bool)
     return bool(_lib.gsx_isect_fused_supported(n_images, tile_w, tile_h, int(packed)))
 
 
-def isect_fused_count_workspace_bytes(rows: int, n_images: int, tile_w: int, tile_h: int) -> int:
-    return int(_lib.gsx_isect_fused_count_workspace_bytes(rows, n_images, tile_w, tile_h))
-
-
-def isect_fused_emit_workspace_bytes(n: int, n_images: int, tile_w: int, tile_h: int) -> int:
-    return int(_lib.gsx_isect_fused_emit_workspace_bytes(n, n_images, tile_w, tile_h))
-
-
-def isect_binned_supported(rows: int, n_images: int, tile_w: int, tile_h: int, packed: bool) -> bool:
-    """Pure query (asking changes nothing)."""
-    return bool(_lib.gsx_isect_binned_supported(rows, n_images, tile_w, tile_h, int(packed)))
-
-
-def isect_binned_should_try(rows: int, n_images: int, tile_w: int, tile_h: int, packed: bool) -> bool:
-    """The decision of ONE intersection (counts a skipped call while a retry note is active): call once, keep the answer."""
-    return bool(_lib.gsx_isect_binned_should_try(rows, n_images, tile_w, tile_h, int(packed)))
-
-
 class IsectPathMemory:
     """The retry notes of the tile-owner-major intersection path, owned by ONE caller (include/gsplat_amd.h:
     gsx_isect_path_memory_*). Which intersection kernel runs depends on recent history (a clustered scene that was sent back is
@@ -332,14 +314,6 @@ class IsectPathMemory:
         h, self._h = getattr(self, "_h", None), None
         if h:
             _lib.gsx_isect_path_memory_destroy(h)
-
-
-def isect_binned_count_workspace_bytes(rows: int, n_images: int, tile_w: int, tile_h: int) -> int:
-    return int(_lib.gsx_isect_binned_count_workspace_bytes(rows, n_images, tile_w, tile_h))
-
-
-def isect_binned_emit_workspace_bytes(n: int) -> int:
-    return int(_lib.gsx_isect_binned_emit_workspace_bytes(n))
 
 
 def copy_column_groups(groups, rows: int) -> None:

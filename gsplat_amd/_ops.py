@@ -54,13 +54,16 @@ def _load_torch_lib() -> None:
 
 _load_torch_lib()
 COMPOSITE_UNAVAILABLE = None  # why the composite ops would be undefined: never, the torch library is required (kept for callers)
-_set_hint_compiled = _cabi.torch_lib().gsx_torch_set_long_tile_hint
 
-# ---- longest tile list: a hint from the orchestrator to the compositing ops ------------------------------------------------
-# rendering.py learns the longest tile list from the intersection's pinned host words; the reference's op schemas have no
-# room for it, so it travels as a per-thread hint around the op call: above SEG_MIN_LONGEST the forward / backward cut long
-# lists into segments that separate workgroups composite (csrc/raster3d_seg.hip). No hint (0) = one workgroup per tile.
-SEG_LEN = int(os.environ.get("GSPLAT_AMD_SEG_LEN", "768"))  # 0 switches segmenting off (A/B); 768: profiles/r11_ab.md #2
+# ---- longest tile list: a note from the intersection to the compositing ops ------------------------------------------------
+# The fused intersection notes the longest tile list of its result under the IDENTITY of flatten_ids' storage (never an
+# address the allocator may hand out again; csrc/torch_ops.cpp keeps the notes as weak references to the StorageImpl). The
+# reference's op schemas have no room for that number, so the compositing forward and backward look their flatten_ids up:
+# above SEG_MIN_LONGEST they cut long lists into segments that separate workgroups composite (csrc/raster3d_seg.hip).
+# Nothing noted (0) or a noted value below 0 = one workgroup per tile.
+# GSPLAT_AMD_SEG_LEN as the compiled forward read it (one reader: csrc/torch_ops.cpp); 0 switches segmenting off (A/B);
+# default 768: profiles/r11_ab.md #2
+SEG_LEN = int(_cabi.torch_lib().gsx_torch_seg_len())
 SEG_MIN_LONGEST = 2 * SEG_LEN if SEG_LEN > 0 else 1 << 62  # lower bound of the cut (csrc/raster3d_seg.hip: seg_cut_for)
 
 
@@ -68,55 +71,17 @@ def _seg_cut(n_isects: int, n_images: int, tw: int, th: int) -> int:
     """Lists longer than this are cut into slices: max(2 slices, 3 x the mean list) - segments are for outliers."""
     return _cabi._lib.gsx_raster3d_seg_cut(int(n_isects), int(n_images), int(tw), int(th), SEG_LEN) if SEG_LEN > 0 else 1 << 62
 
-_hint = __import__("threading").local()
 
-
-def long_tile_hint() -> int:
-    return getattr(_hint, "longest", 0)
-
-
-def long_tile_hint_of_call() -> int:
-    """What the caller set around the op call in flight - still readable after the op body consumed long_tile_hint()
-    (the autograd setup_context stores it for the backward)."""
-    return getattr(_hint, "of_call", 0)
-
-
-def set_long_tile_hint(longest: int) -> None:
-    """Called by the WRAPPER around an op call (and with 0 in its finally block). The compiled compositing forward reads its
-    own copy (gsx_torch_set_long_tile_hint), the Python backward bodies this one."""
-    _hint.longest = _hint.of_call = int(longest)
-    _set_hint_compiled(int(longest))
-
-
-def _consume_long_tile_hint() -> int:
-    """Called by an op BODY: returns the hint and clears it for nested calls, but leaves long_tile_hint_of_call() alone - the
-    autograd setup_context runs after the body and stores it for the backward."""
-    longest = getattr(_hint, "longest", 0)
-    _hint.longest = 0
-    return longest
-
-# Stage-level callers (isect_tiles -> isect_offset_encode -> rasterize_to_pixels without rasterization() in between) have no
-# orchestrator to carry the hint: the intersection notes the longest list of its result and a compositing call without a hint
-# looks its flatten_ids up. A note is keyed by the IDENTITY of the tensor's storage, never by an address the allocator may hand
-# out again; csrc/torch_ops.cpp keeps the notes (weak references to the StorageImpl), for the compiled and the Python bodies.
-
-
-def _lookup_longest(flatten_ids: Tensor) -> int:
-    return int(torch.ops.gsplat_amd.lookup_longest(flatten_ids))
-
-
-# The segment workspace of a compositing forward, for the backward over the same lists (csrc/raster3d_seg.hip:
-# gsx_raster3d_bwd_seg_reuse). The notes live in libgsplat_amd_torch.so (csrc/torch_ops.cpp: keyed by the identity of last_ids,
-# written by the compiled forward body).
-_SEG_REUSE = os.environ.get("GSPLAT_AMD_SEG_REUSE", "1") not in ("0", "")
+_lookup_longest = torch.ops.gsplat_amd.lookup_longest.default  # (flatten_ids) -> int; the overload: no resolution per call
 
 
 def _lookup_seg_workspace(last_ids: Tensor, n_isects: int, D: int, inputs) -> Optional[Tensor]:
-    """`inputs`: (means2d, conics, colors, opacities, isect_offsets, flatten_ids) as the op received them - the note only serves
-    a backward that brings the same tensors, unwritten since (address + version counter)."""
-    if _SEG_REUSE:
-        return torch.ops.gsplat_amd.lookup_seg_workspace(last_ids, int(n_isects), int(D), SEG_LEN, list(inputs))
-    return None
+    """The segment workspace of the compositing forward that returned `last_ids`, for the backward over the same lists
+    (csrc/raster3d_seg.hip: gsx_raster3d_bwd_seg_reuse); noted by the compiled forward body (csrc/torch_ops.cpp), not at all
+    under GSPLAT_AMD_SEG_REUSE=0. `inputs`: (means2d, conics, colors, opacities, isect_offsets, flatten_ids) as the op received
+    them - the note only serves a backward that brings the same tensors, unwritten since (identity + version counter)."""
+    return torch.ops.gsplat_amd.lookup_seg_workspace(last_ids, int(n_isects), int(D), SEG_LEN, list(inputs))
+
 
 SCHEMAS = {
     # gsplat/cuda/ext.cpp:984-991
@@ -548,11 +513,13 @@ class _IsectPending:
 
 
 def isect_begin(means2d, radii, depths, conics, opacities, image_ids, gaussian_ids, n_images, tile_size,
-                tile_width, tile_height, sort, segmented) -> "_IsectPending":
+                tile_width, tile_height, sort, segmented, tile_mask=None) -> "_IsectPending":
     """First half of intersect_tile: count tiles per Gaussian, prefix-sum, and START the device->host read of the
     total (pinned buffer + event) without waiting for it. The caller may enqueue independent work (the orchestrator
     runs the SH kernels here) before isect_finish() blocks on the event, so the host round trip for the exact output
-    length (reference: the `.item()` at Intersect.cpp:258-259) no longer idles the GPU."""
+    length (reference: the `.item()` at Intersect.cpp:258-259) no longer idles the GPU.
+    `tile_mask` (intersect_tile_sparse; fused path only): bool flags per (image, tile), only flagged tiles receive
+    intersections; no tiles_per_gauss is made then."""
     f64 = means2d.dtype == torch.float64
     if f64:
         # float64 rows (the reference dispatches this op over float and double): radius boxes in double, keys carry the
@@ -590,7 +557,7 @@ def isect_begin(means2d, radii, depths, conics, opacities, image_ids, gaussian_i
         )
     dev = means2d.device
     st = _IsectPending()
-    st.args = (means2d, radii, depths, conics, opacities, image_ids)
+    st.args = (means2d, radii, depths, conics, opacities, image_ids, tile_mask)
     st.rows, st.n_per, st.I, st.sort = rows, n_per, I, sort
     st.geom = (tile_size, tile_width, tile_height, tile_bits, image_bits)
     st.tiles_per_gauss = torch.empty(out_shape, device=dev, dtype=torch.int32)
@@ -604,8 +571,11 @@ def isect_begin(means2d, radii, depths, conics, opacities, image_ids, gaussian_i
     st.fused = bool(sort) and not f64 and _cabi.isect_fused_supported(I, tile_width, tile_height, packed)
     if st.fused:
         st.tiles_per_gauss, st.offsets, st.count_ws, st.host_total = torch.ops.gsplat_amd.isect_fused_begin(
-            means2d, radii, depths, conics, opacities, rows, I, tile_size, tile_width, tile_height, list(out_shape))
+            means2d, radii, depths, conics, opacities, tile_mask, rows, I, tile_size, tile_width, tile_height,
+            [] if tile_mask is not None else list(out_shape))
         return st
+    if tile_mask is not None:
+        raise RuntimeError("isect_begin: a tile_mask needs the fused path (sort=True, float32, isect_fused_supported)")
     st.host_total = torch.zeros(1, dtype=torch.int64, pin_memory=True)  # n_isects
     if f64:
         call("gsx_isect_count_f64", ptr(means2d), ptr(radii), ptr(image_ids), rows, n_per, I, tile_size, tile_width,
@@ -620,14 +590,9 @@ def isect_begin(means2d, radii, depths, conics, opacities, image_ids, gaussian_i
     return st
 
 
-def isect_max_tile_len(st: "_IsectPending") -> int:
-    """Length of the longest tile list (0 when the path taken does not report it). Valid after isect_finish()."""
-    return int(st.host_total[1].item()) if st.fused else 0
-
-
 def isect_finish(st: "_IsectPending"):
     """Second half of intersect_tile: wait for the total, allocate exact-length outputs, emit (key, value) pairs, sort."""
-    means2d, radii, depths, conics, opacities, image_ids = st.args
+    means2d, radii, depths, conics, opacities, image_ids, tile_mask = st.args
     tile_size, tile_width, tile_height, tile_bits, image_bits = st.geom
     rows, n_per, I = st.rows, st.n_per, st.I
     dev = means2d.device
@@ -637,8 +602,8 @@ def isect_finish(st: "_IsectPending"):
                 torch.empty(0, device=dev, dtype=torch.int32))
     if st.fused:  # compiled second half: waits for the count (the one host round trip), allocates, emits, sorts, notes
         isect_ids, flatten_ids = torch.ops.gsplat_amd.isect_fused_finish(
-            means2d, radii, depths, conics, opacities, rows, I, tile_size, tile_width, tile_height, st.count_ws, st.offsets,
-            st.host_total, tiles_per_gauss)
+            means2d, radii, depths, conics, opacities, tile_mask, rows, I, tile_size, tile_width, tile_height, st.count_ws,
+            st.offsets, st.host_total, tiles_per_gauss)
         return tiles_per_gauss, isect_ids, flatten_ids
     st.event.synchronize()  # host sync: exact-length outputs (reference: Intersect.cpp:258-259)
     n_isects = int(st.host_total[0].item())
@@ -655,20 +620,25 @@ def isect_finish(st: "_IsectPending"):
     else:
         call("gsx_isect_emit", ptr(means2d), ptr(radii), ptr(depths), ptr(conics), ptr(opacities), ptr(image_ids),
              ptr(cum), rows, n_per, I, tile_size, tile_width, tile_height, ptr(isect_ids), ptr(flatten_ids))
-    if st.sort and _cabi.tile_sort_supported(I, tile_width, tile_height):
-        keys_s, vals_s = torch.empty_like(isect_ids), torch.empty_like(flatten_ids)
-        ws = torch.empty(_cabi.tile_sort_workspace_bytes(n_isects, I, tile_width, tile_height), device=dev,
-                         dtype=torch.uint8)
-        call("gsx_isect_tile_sort", ptr(isect_ids), ptr(flatten_ids), n_isects, I, tile_width, tile_height,
-             ptr(keys_s), ptr(vals_s), ptr(ws), ws.numel())
-        isect_ids, flatten_ids = keys_s, vals_s
-    elif st.sort:
-        keys_alt, vals_alt = torch.empty_like(isect_ids), torch.empty_like(flatten_ids)
-        ws = torch.empty(_cabi.sort_workspace_bytes(n_isects), device=dev, dtype=torch.uint8)
-        in_alt = _cabi.sort_pairs(isect_ids, flatten_ids, keys_alt, vals_alt, n_isects, 32 + tile_bits + image_bits, ws)
-        if in_alt:
-            isect_ids, flatten_ids = keys_alt, vals_alt
+    if st.sort:
+        isect_ids, flatten_ids = _sort_isects(isect_ids, flatten_ids, I, tile_width, tile_height, 32 + tile_bits + image_bits)
     return tiles_per_gauss, isect_ids, flatten_ids
+
+
+def _sort_isects(isect_ids, flatten_ids, I, tw, th, key_bits):
+    """(isect_ids, flatten_ids) sorted by key: the per-tile sort where the tile grid allows it, else the radix sort over the
+    low `key_bits` bits. Returns the buffers that hold the sorted pairs."""
+    n, dev = isect_ids.numel(), isect_ids.device
+    keys_alt, vals_alt = torch.empty_like(isect_ids), torch.empty_like(flatten_ids)
+    if _cabi.tile_sort_supported(I, tw, th):
+        ws = torch.empty(_cabi.tile_sort_workspace_bytes(n, I, tw, th), device=dev, dtype=torch.uint8)
+        call("gsx_isect_tile_sort", ptr(isect_ids), ptr(flatten_ids), n, I, tw, th, ptr(keys_alt), ptr(vals_alt), ptr(ws),
+             ws.numel())
+        return keys_alt, vals_alt
+    ws = torch.empty(_cabi.sort_workspace_bytes(n), device=dev, dtype=torch.uint8)
+    if _cabi.sort_pairs(isect_ids, flatten_ids, keys_alt, vals_alt, n, key_bits, ws):
+        return keys_alt, vals_alt
+    return isect_ids, flatten_ids
 
 
 @_op("intersect_tile")
@@ -752,18 +722,8 @@ def intersect_tile_lidar(lidar, means2d, radii, depths, image_ids, gaussian_ids,
     call("gsx_isect_lidar_emit", ptr(means2d), r_i, r_f, ptr(depths), ptr(img), ptr(cum), rows, n_per_arg, I, *targs,
          ptr(isect_ids), ptr(flatten_ids))
     if sort:
-        tw, th = int(lidar.n_bins_azimuth), int(lidar.n_bins_elevation)
-        if _cabi.tile_sort_supported(I, tw, th):
-            keys_s, vals_s = torch.empty_like(isect_ids), torch.empty_like(flatten_ids)
-            ws = torch.empty(_cabi.tile_sort_workspace_bytes(n_isects, I, tw, th), device=dev, dtype=torch.uint8)
-            call("gsx_isect_tile_sort", ptr(isect_ids), ptr(flatten_ids), n_isects, I, tw, th, ptr(keys_s), ptr(vals_s), ptr(ws),
-                 ws.numel())
-            isect_ids, flatten_ids = keys_s, vals_s
-        else:
-            keys_alt, vals_alt = torch.empty_like(isect_ids), torch.empty_like(flatten_ids)
-            ws = torch.empty(_cabi.sort_workspace_bytes(n_isects), device=dev, dtype=torch.uint8)
-            if _cabi.sort_pairs(isect_ids, flatten_ids, keys_alt, vals_alt, n_isects, 32 + tile_bits + image_bits, ws):
-                isect_ids, flatten_ids = keys_alt, vals_alt
+        isect_ids, flatten_ids = _sort_isects(isect_ids, flatten_ids, I, int(lidar.n_bins_azimuth), int(lidar.n_bins_elevation),
+                                              32 + tile_bits + image_bits)
     return tiles_per_gauss, isect_ids, flatten_ids
 
 
@@ -943,7 +903,9 @@ def _pixel_linear_strides(t):
 @_op("rasterize_to_pixels_3dgs_bwd")
 def rasterize_to_pixels_3dgs_bwd(means2d, conics, colors, opacities, backgrounds, masks, tile_offsets, flatten_ids,
                                  render_alphas, last_ids, image_width, image_height, tile_size, absgrad,
-                                 v_render_colors, v_render_alphas, compute_v_backgrounds):
+                                 v_render_colors, v_render_alphas, compute_v_backgrounds, *, _longest=None):
+    """`_longest` (private, gsplat_amd's own autograd only): the longest tile list as the forward's setup_context looked it
+    up; a call through the dispatcher (the reference's Python, the raw op) looks up what the intersection noted."""
     image_dims, I, th, tw, D = _raster_dims(tile_offsets, colors)
     as_received = (means2d, conics, colors, opacities, tile_offsets, flatten_ids)  # key of the segment-workspace note
     means2d, conics, colors, opacities = (means2d.contiguous(), conics.contiguous(), colors.contiguous(),
@@ -955,7 +917,7 @@ def rasterize_to_pixels_3dgs_bwd(means2d, conics, colors, opacities, backgrounds
     # line, which is what makes the kernel's atomic flush cheap; projection_ewa_3dgs_*_bwd reads the views in place.
     R = opacities.numel()
     geo = 8 if absgrad else 6
-    longest = _consume_long_tile_hint() or _lookup_longest(flatten_ids)  # set by the autograd formula around this call
+    longest = _longest if _longest is not None else _lookup_longest(flatten_ids)
     segmented = (longest > SEG_MIN_LONGEST and not absgrad and D <= 4 and tile_size == 16
                  and longest > _seg_cut(flatten_ids.numel(), I, tw, th))
     # the per-tile launch zero-fills the rows itself (inside its tile-order kernel: gsx_raster3d_bwd_fill)
@@ -1476,47 +1438,12 @@ def intersect_tile_sparse(means2d, radii, depths, image_ids, tile_mask, active_t
         # the dense fused path with the tile mask applied inside the walk (AABB test: conics / opacities NULL, as the
         # reference's sparse enumeration, Intersect.cpp:617-634): inactive tiles get empty segments, so the dense
         # offsets of the active tiles ARE the compacted offsets
-        offsets = torch.empty(I * n_tiles, device=dev, dtype=torch.int32)
-        host_total = torch.zeros(2, dtype=torch.int64, pin_memory=True)  # [n_isects, longest tile list]
-        geom = (rows, I, tile_size, tile_width, tile_height)
-        hosts = (_cabi.ptr_host(host_total), _cabi.ptr_host(host_total) + 8)
-
-        def count(binned):  # the tile-owner-major count (csrc/isect_binned.hip) or the Gaussian-major one (isect_fused.hip)
-            if binned:
-                ws = torch.empty(_cabi.isect_binned_count_workspace_bytes(rows, I, tile_width, tile_height), device=dev,
-                                 dtype=torch.uint8)
-                call("gsx_isect_binned_count", ptr(means2d), ptr(radii), ptr(depths), None, None, ptr(tile_mask), *geom, None,
-                     ptr(offsets), *hosts, ptr(ws), ws.numel())
-            else:
-                ws = torch.empty(_cabi.isect_fused_count_workspace_bytes(rows, I, tile_width, tile_height), device=dev,
-                                 dtype=torch.uint8)
-                call("gsx_isect_fused_count", ptr(means2d), ptr(radii), None, None, ptr(tile_mask), *geom, None, ptr(offsets),
-                     *hosts, ptr(ws), ws.numel())
-            torch.cuda.current_stream(dev).synchronize()  # host sync: exact-length outputs (reference: Intersect.cpp:637)
-            return ws, int(host_total[0].item())
-
-        binned = _cabi.isect_binned_should_try(rows, I, tile_width, tile_height, packed)  # once: the emit follows the count
-        count_ws, n_isects = count(binned)
-        if binned and n_isects == -2:  # GSX_ISECT_RETRY: count again Gaussian-major, not tried again for the next 63 calls
-            binned = False
-            _cabi._lib.gsx_isect_binned_note_retry(rows, I, tile_width, tile_height)
-            count_ws, n_isects = count(False)
-        if n_isects >= 2**31:
-            raise RuntimeError(f"intersect_tile: {n_isects} intersections overflow the int32 index space")
-        if n_isects == 0:
+        st = isect_begin(means2d, radii, depths, None, None, image_ids if packed else None, None, I, tile_size, tile_width,
+                         tile_height, True, False, tile_mask=tile_mask)
+        _tpg, _isect_ids, flatten_ids = isect_finish(st)
+        if flatten_ids.shape[0] == 0:
             return empty
-        isect_ids = torch.empty(n_isects, device=dev, dtype=torch.int64)
-        flatten_ids = torch.empty(n_isects, device=dev, dtype=torch.int32)
-        if binned:
-            ws = torch.empty(_cabi.isect_binned_emit_workspace_bytes(n_isects), device=dev, dtype=torch.uint8)
-            call("gsx_isect_binned_emit_sort", *geom, ptr(count_ws), count_ws.numel(), ptr(offsets), n_isects,
-                 int(host_total[1].item()), ptr(isect_ids), ptr(flatten_ids), ptr(ws), ws.numel())
-        else:
-            ws = torch.empty(_cabi.isect_fused_emit_workspace_bytes(n_isects, I, tile_width, tile_height), device=dev,
-                             dtype=torch.uint8)
-            call("gsx_isect_fused_emit_sort", ptr(means2d), ptr(radii), ptr(depths), None, None, ptr(tile_mask), *geom,
-                 ptr(count_ws), count_ws.numel(), ptr(offsets), n_isects, ptr(isect_ids), ptr(flatten_ids), ptr(ws), ws.numel())
-        return torch.cat([offsets[active_tiles.long()], sentinel(n_isects)]), flatten_ids
+        return torch.cat([st.offsets[active_tiles.long()], sentinel(flatten_ids.shape[0])]), flatten_ids
     # packed rows of several images / tile grids beyond the fused path's LDS histogram: enumerate every tile with the
     # generic kernels, then drop the intersections of inactive tiles (order within a tile is preserved)
     if image_ids is not None:

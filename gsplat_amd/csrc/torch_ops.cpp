@@ -23,6 +23,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <mutex>
 #include <set>
@@ -125,6 +126,26 @@ int64_t prod(c10::IntArrayRef dims)
     return p;
 }
 
+// A pinned host word that a kernel overwrites (a count the host needs for exact-length outputs): polled instead of
+// synchronising the stream, so that the kernels enqueued behind the writer keep running and the caller can go on enqueuing.
+// Spins while pending(word); the wait is ~10-100 us, so it yields now and then instead of pinning a core at 100 %. After
+// `timeout` the stream is synchronised (never seen; keeps the wait correct if the store is not host-visible before the
+// stream drains).
+template <class Pending>
+int64_t poll_host_word(volatile const int64_t *slot, Pending pending, c10::hip::HIPStreamMasqueradingAsCUDA stream,
+                       std::chrono::seconds timeout)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint64_t spin = 0;; ++spin) {
+        const int64_t v = *slot;
+        if (!pending(v) && v == *slot) return v; // two equal reads: a value caught half-written cannot pass
+        if ((spin & 63u) == 63u) std::this_thread::yield();
+        if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > timeout) break;
+    }
+    stream.synchronize();
+    return *slot;
+}
+
 // ---- projection (dense) ------------------------------------------------------------------------------------------------
 std::tuple<Tensor, Tensor, Tensor, Tensor, OptTensor>
 projection_ewa_3dgs_fused(const Tensor &means_, const OptTensor &covars_, const OptTensor &quats_, const OptTensor &scales_,
@@ -215,20 +236,9 @@ projection_ewa_3dgs_packed(const Tensor &means_, const OptTensor &covars_, const
                                        calc_compensations ? 1 : 0, mp<int32_t>(blocks), mp<int32_t>(blocks) + n_blocks, nullptr,
                                        host_nnz.mutable_data_ptr<int64_t>(), L.stream),
           "gsx_project_ewa_packed_count_blocks"); }
-    // The row count is on the host once the SCAN has run - the write kernel enqueued after it does not have to finish first.
-    // Polling the pinned word instead of synchronising the stream lets the caller slice the outputs and enqueue the next
-    // kernels while the write kernel still runs (everything stays stream-ordered behind it).
-    auto wait_nnz = [&]() -> int64_t {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint64_t spin = 0;; ++spin) {
-            const int64_t v = *nnz_slot;
-            if (v >= 0 && v == *nnz_slot) return v; // two equal reads: a value caught half-written cannot pass
-            if ((spin & 63u) == 63u) std::this_thread::yield();
-            if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-        }
-        stream.synchronize(); // never seen; keeps the function correct if the copy is not host-visible before the stream drains
-        return *nnz_slot;
-    };
+    // The row count is on the host once the SCAN has run - the write kernel enqueued after it does not have to finish first:
+    // the caller slices the outputs and enqueues the next kernels while the write kernel still runs (poll_host_word).
+    auto wait_nnz = [&] { return poll_host_word(nnz_slot, [](int64_t v) { return v < 0; }, stream, std::chrono::seconds(2)); };
     auto write = [&](int64_t rows, decltype(outputs(0)) &o) {
         auto &[bi, ci, gi, indptr, radii, m2, dep, con, comp] = o;
         (void)rows;
@@ -258,106 +268,129 @@ projection_ewa_3dgs_packed(const Tensor &means_, const OptTensor &covars_, const
     if (nnz > 0 || true) write(nnz, o);
     return o;
 }
-// ---- longest tile list of an intersection result, for the compositing calls that consume it ---------------------------
-// A caller that drives the STAGE ops itself (the reference's isect_tiles -> isect_offset_encode -> rasterize_to_pixels, e.g.
-// its own Python over this shim) has no orchestrator to carry the hint: the intersection notes the longest list of the result
-// it returns under the address + length of `flatten_ids`, and a compositing call without a hint looks its `flatten_ids` up.
-// The key is the IDENTITY OF THE STORAGE, not an address: a note holds a weak reference to the StorageImpl of the tensor it was
-// taken for, which keeps that object's address from being handed out again for as long as the note exists - a later tensor
-// that the allocator placed at the same device address has another StorageImpl and does not match (round 4 keyed the notes by
-// data pointer + length: after allocator reuse a stage-level call could pick up another intersection's value, and which
-// kernel ran - and so the float summation order - depended on the process' history).
-struct LongestNote {
-    std::optional<c10::weak_intrusive_ptr<c10::StorageImpl>> storage; // empty slot: no value
-    int64_t offset = 0, n = 0, longest = 0;
+// ---- notes: what one op call leaves for a later one that the reference's op schemas have no slot for ------------------
+// A note is keyed by the IDENTITY of a tensor, never by an address: a weak reference to its StorageImpl plus offset and
+// length. The weak reference keeps that object's address from being handed out again for as long as the note exists, so a
+// later tensor that the allocator placed at the same device address has another StorageImpl and does not match (keyed by
+// data pointer, a call could pick up another intersection's value after allocator reuse, and which kernel ran - and so the
+// float summation order - depended on the process' history).
+struct TensorKey {
+    std::optional<c10::weak_intrusive_ptr<c10::StorageImpl>> storage; // empty: no tensor
+    int64_t offset = 0, n = 0;
+    TensorKey() = default;
+    explicit TensorKey(const Tensor &t)
+    {
+        if (!t.defined() || t.numel() <= 0 || !t.has_storage()) return;
+        storage = c10::weak_intrusive_ptr<c10::StorageImpl>(
+            c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(t.storage().unsafeGetStorageImpl()));
+        offset = t.storage_offset(); n = t.numel();
+    }
     const c10::StorageImpl *target() const { return storage ? storage->_unsafe_get_target() : nullptr; }
+    bool expired() const { return storage && storage->expired(); }
+    bool same_storage(const Tensor &t) const
+    {
+        return storage && t.defined() && t.has_storage() && target() == t.storage().unsafeGetStorageImpl();
+    }
+    bool matches(const Tensor &t) const { return same_storage(t) && offset == t.storage_offset() && n == t.numel(); }
+};
+// The slot a fresh note for `t` goes to: the one that holds t's storage already (noting again replaces), else a free one
+// (never used, or its tensor has died), and only then the oldest.
+static std::atomic<uint64_t> g_note_seq{0}; // orders the notes of a table by age
+template <class Note, size_t N> Note &note_slot(Note (&table)[N], const Tensor &t)
+{
+    Note *pick = nullptr;
+    for (auto &e : table)
+        if (e.key.same_storage(t)) return e;
+    for (auto &e : table)
+        if (!e.key.storage || e.key.expired()) return e;
+    for (auto &e : table)
+        if (!pick || e.seq < pick->seq) pick = &e;
+    return *pick;
+}
+
+// ---- longest tile list of an intersection result, for the compositing calls that consume it ---------------------------
+// The fused intersection notes the longest list of the result it returns under the identity of `flatten_ids`; the
+// compositing forward and backward look their `flatten_ids` up and cut long lists into segments above
+// gsx_raster3d_seg_cut() (csrc/raster3d_seg.hip). This is the ONLY channel for that number, for rasterization() and for a
+// caller that drives the stage ops itself (isect_tiles -> isect_offset_encode -> rasterize_to_pixels) alike. 0 = nothing
+// noted: one workgroup per tile; a noted value below 0 says the same on purpose. A note that has not been consumed yet is
+// lost only if 16 other intersections, whose flatten_ids are all still alive, are noted between an intersection and its
+// compositing call: a fresh note takes a slot whose tensor has died before it takes the oldest.
+struct LongestNote {
+    TensorKey key;
+    uint64_t seq = 0;
+    int64_t longest = 0;
 };
 static std::mutex g_notes_mu;
 static LongestNote g_notes[16];
-static unsigned g_notes_next = 0;
 void note_longest(const Tensor &flat, int64_t longest)
 {
-    if (!flat.defined() || flat.numel() <= 0 || !flat.has_storage()) return;
-    c10::StorageImpl *impl = flat.storage().unsafeGetStorageImpl();
+    TensorKey key(flat);
+    if (!key.storage) return;
     std::lock_guard<std::mutex> lock(g_notes_mu);
-    LongestNote fresh;
-    fresh.storage = c10::weak_intrusive_ptr<c10::StorageImpl>(c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(impl));
-    fresh.offset = flat.storage_offset(); fresh.n = flat.numel(); fresh.longest = longest;
-    for (auto &e : g_notes)
-        if (e.target() == impl) { e = std::move(fresh); return; }
-    g_notes[g_notes_next++ % 16u] = std::move(fresh);
+    note_slot(g_notes, flat) = LongestNote{std::move(key), ++g_note_seq, longest};
 }
 int64_t lookup_longest(const Tensor &flat)
 {
-    if (!flat.defined() || flat.numel() <= 0 || !flat.has_storage()) return 0;
-    const c10::StorageImpl *impl = flat.storage().unsafeGetStorageImpl();
     std::lock_guard<std::mutex> lock(g_notes_mu);
     for (const auto &e : g_notes)
-        if (e.target() == impl && e.offset == flat.storage_offset() && e.n == flat.numel()) return e.longest;
+        if (e.key.matches(flat)) return e.longest;
     return 0;
 }
 
 // ---- the segment workspace of a compositing FORWARD, for the backward over the same lists ------------------------------
 // gsx_raster3d_fwd_seg leaves every slice's colour sums and end transmittance in its workspace; a backward that still has it
-// needs no pre-pass (gsx_raster3d_bwd_seg_reuse). The reference's op schemas have no slot for a workspace, so the forward
-// body notes it under the identity of the `last_ids` it returns (the tensor every autograd formula - this package's and the
-// reference's own - saves and hands to the backward op), the same way the longest list is noted above: a weak reference to
-// the StorageImpl, never an address. The workspace itself is held STRONGLY (tens of MB for a 1080p scene) in a ring of four;
-// a note whose last_ids died is dropped at the next call of either function.
+// needs no pre-pass (gsx_raster3d_bwd_seg_reuse). The forward body notes it under the identity of the `last_ids` it returns
+// (the tensor every autograd formula - this package's and the reference's own - saves and hands to the backward op). The
+// workspace itself is held STRONGLY (tens of MB for a 1080p scene) in a table of four; a note whose last_ids died is
+// dropped at the next call of either function.
+// The sums in the workspace belong to the forward's INPUTS: a backward call that brings other tensors than the forward saw
+// (identity), or the same ones written to since (version counter), gets no workspace and runs its pre-pass on what it was
+// given.
 struct SegWsNote {
-    std::optional<c10::weak_intrusive_ptr<c10::StorageImpl>> storage;
-    int64_t offset = 0, n = 0, n_isects = 0, cdim = 0, seg_len = 0;
-    std::vector<int64_t> inputs; // (address, version) of every tensor the forward composited from: see seg_ws_inputs_key
+    TensorKey key;
+    uint64_t seq = 0;
+    int64_t n_isects = 0, cdim = 0, seg_len = 0;
+    std::vector<std::pair<TensorKey, int64_t>> inputs; // (identity, version) of every tensor the forward composited from
     Tensor ws;
-    const c10::StorageImpl *target() const { return storage ? storage->_unsafe_get_target() : nullptr; }
+    bool made_from(at::TensorList ts) const
+    {
+        if (ts.size() != inputs.size()) return false;
+        for (size_t i = 0; i < inputs.size(); ++i)
+            if (!inputs[i].first.matches(ts[i]) || inputs[i].second != tensor_version(ts[i])) return false;
+        return true;
+    }
+    static int64_t tensor_version(const Tensor &t) { return t.defined() && !t.is_inference() ? (int64_t)t._version() : 0; }
 };
 static std::mutex g_seg_ws_mu;
 static SegWsNote g_seg_ws[4];
-static unsigned g_seg_ws_next = 0;
-// The sums in the workspace belong to the forward's INPUTS: a backward call that brings other tensors than the forward saw, or
-// the same ones written to since (version counter), gets no workspace and runs its pre-pass on what it was given.
-static std::vector<int64_t> seg_ws_inputs_key(at::TensorList inputs)
-{
-    std::vector<int64_t> k;
-    for (const Tensor &t : inputs) {
-        k.push_back(t.defined() ? (int64_t)reinterpret_cast<intptr_t>(t.const_data_ptr()) : 0);
-        k.push_back(t.defined() && !t.is_inference() ? (int64_t)t._version() : 0);
-    }
-    return k;
-}
 static void seg_ws_purge_locked()
 {
     for (auto &e : g_seg_ws)
-        if (e.storage && e.storage->expired()) e = SegWsNote();
+        if (e.key.expired()) e = SegWsNote();
 }
 void note_seg_workspace(const Tensor &last_ids, const Tensor &ws, int64_t n_isects, int64_t cdim, int64_t seg_len,
                         at::TensorList inputs)
 {
-    if (!last_ids.defined() || last_ids.numel() <= 0 || !last_ids.has_storage()) return;
-    c10::StorageImpl *impl = last_ids.storage().unsafeGetStorageImpl();
-    std::lock_guard<std::mutex> lock(g_seg_ws_mu);
-    seg_ws_purge_locked();
     SegWsNote fresh;
-    fresh.storage = c10::weak_intrusive_ptr<c10::StorageImpl>(c10::intrusive_ptr<c10::StorageImpl>::reclaim_copy(impl));
-    fresh.offset = last_ids.storage_offset(); fresh.n = last_ids.numel();
+    fresh.key = TensorKey(last_ids);
+    if (!fresh.key.storage) return;
     fresh.n_isects = n_isects; fresh.cdim = cdim; fresh.seg_len = seg_len; fresh.ws = ws;
-    fresh.inputs = seg_ws_inputs_key(inputs);
-    for (auto &e : g_seg_ws)
-        if (e.target() == impl) { e = std::move(fresh); return; }
-    g_seg_ws[g_seg_ws_next++ % 4u] = std::move(fresh);
-}
-Tensor lookup_seg_workspace(const Tensor &last_ids, int64_t n_isects, int64_t cdim, int64_t seg_len, at::TensorList inputs)
-{
-    if (!last_ids.defined() || last_ids.numel() <= 0 || !last_ids.has_storage()) return Tensor();
-    const c10::StorageImpl *impl = last_ids.storage().unsafeGetStorageImpl();
+    for (const Tensor &t : inputs) fresh.inputs.emplace_back(TensorKey(t), SegWsNote::tensor_version(t));
     std::lock_guard<std::mutex> lock(g_seg_ws_mu);
     seg_ws_purge_locked();
-    const std::vector<int64_t> key = seg_ws_inputs_key(inputs);
+    fresh.seq = ++g_note_seq;
+    note_slot(g_seg_ws, last_ids) = std::move(fresh);
+}
+OptTensor lookup_seg_workspace(const Tensor &last_ids, int64_t n_isects, int64_t cdim, int64_t seg_len, at::TensorList inputs)
+{
+    std::lock_guard<std::mutex> lock(g_seg_ws_mu);
+    seg_ws_purge_locked();
     for (const auto &e : g_seg_ws)
-        if (e.target() == impl && e.inputs == key && e.offset == last_ids.storage_offset() && e.n == last_ids.numel() && e.n_isects == n_isects
-            && e.cdim == cdim && e.seg_len == seg_len && e.ws.defined() && e.ws.device() == last_ids.device())
+        if (e.key.matches(last_ids) && e.made_from(inputs) && e.n_isects == n_isects && e.cdim == cdim && e.seg_len == seg_len
+            && e.ws.defined() && e.ws.device() == last_ids.device())
             return e.ws;
-    return Tensor();
+    return std::nullopt;
 }
 static bool seg_reuse_env()
 {
@@ -398,10 +431,6 @@ RasterDims raster_dims(const Tensor &isect_offsets, const Tensor &colors)
     return r;
 }
 
-// Longest tile list of the intersection the NEXT compositing call consumes, set by the orchestrator (rendering.py knows it
-// from the intersection's host word; the reference's op schema has no room for it). Above gsx_raster3d_seg_cut() the forward cuts
-// long lists into segments (csrc/raster3d_seg.hip). 0 = unknown: one workgroup per tile. Consumed (reset) by the call.
-thread_local int64_t g_long_tile_hint = 0;
 // segment length / the longest list from which segmenting starts; GSPLAT_AMD_SEG_LEN overrides (A/B), 0 switches it off
 static int64_t seg_len_env()
 {
@@ -437,9 +466,7 @@ rasterize_to_pixels_3dgs(const Tensor &means2d_, const Tensor &conics_, const Te
     Tensor renders = at::empty(shape({height, width, r.D}), means2d.options());
     Tensor alphas = at::empty(shape({height, width, 1}), means2d.options());
     Tensor last_ids = at::empty(shape({height, width}), means2d.options().dtype(at::kInt));
-    int64_t longest = g_long_tile_hint;
-    g_long_tile_hint = 0;
-    if (longest == 0) longest = lookup_longest(flatten_ids_); // stage-level caller: no orchestrator hint
+    const int64_t longest = lookup_longest(flatten_ids_); // what the intersection that made these lists noted
     if (kSegLen > 0 && longest > gsx_raster3d_seg_cut(flat.numel(), (uint32_t)r.I, (uint32_t)r.tw, (uint32_t)r.th, (uint32_t)kSegLen)) {
         Tensor ws = at::empty({gsx_raster3d_seg_workspace_bytes(flat.numel(), (uint32_t)r.I, (uint32_t)r.tw, (uint32_t)r.th, (uint32_t)r.D,
                                                               (uint32_t)kSegLen)}, means2d.options().dtype(at::kByte));
@@ -467,13 +494,25 @@ rasterize_to_pixels_3dgs(const Tensor &means2d_, const Tensor &conics_, const Te
 // The orchestrators (rendering.py) enqueue the SH kernels between the halves instead of blocking on the intersection count;
 // private ops (namespace gsplat_amd: not part of the reference's surface). The count travels through a pinned host word initialised to a
 // sentinel: the second half polls it - no event, no stream synchronisation, and the kernels enqueued in between keep running.
-std::tuple<Tensor, Tensor, Tensor, Tensor>
+// This is the one place where the host protocol of the fused intersection lives (decide the path once, count, wait, count
+// again Gaussian-major on GSX_ISECT_RETRY, emit): the sparse intersection comes through here too, with its `tile_mask` (only
+// flagged tiles receive intersections) and an empty `out_shape` (= no tiles_per_gauss wanted).
+const uint8_t *mask_ptr(const OptTensor &m) { return has(m) && m->numel() ? (const uint8_t *)m->const_data_ptr<bool>() : nullptr; }
+
+std::tuple<OptTensor, Tensor, Tensor, Tensor>
 isect_fused_begin(const Tensor &means2d, const Tensor &radii, const Tensor &depths, const OptTensor &conics, const OptTensor &opac,
-                  int64_t rows, int64_t I, int64_t tile_size, int64_t tile_w, int64_t tile_h, c10::IntArrayRef out_shape)
+                  const OptTensor &tile_mask, int64_t rows, int64_t I, int64_t tile_size, int64_t tile_w, int64_t tile_h, c10::IntArrayRef out_shape)
 {
     Launch L(means2d);
     const uint32_t uI = (uint32_t)I, uts = (uint32_t)tile_size, utw = (uint32_t)tile_w, uth = (uint32_t)tile_h;
-    Tensor tiles_per_gauss = at::empty(out_shape, means2d.options().dtype(at::kInt));
+    TORCH_CHECK(!has(tile_mask) || (tile_mask->scalar_type() == at::kBool && tile_mask->is_contiguous()
+                                    && tile_mask->numel() == I * tile_w * tile_h),
+                "isect_fused_begin: tile_mask must be a contiguous bool tensor of n_images * tiles flags");
+    Tensor tiles_per_gauss; // stays undefined (a null pointer for the kernels, None for the caller) when none is wanted
+    if (!out_shape.empty()) tiles_per_gauss = at::empty(out_shape, means2d.options().dtype(at::kInt));
+    auto result = [&](const Tensor &offsets, const Tensor &count_ws, const Tensor &host_total) {
+        return std::make_tuple(tiles_per_gauss.defined() ? OptTensor(tiles_per_gauss) : OptTensor(), offsets, count_ws, host_total);
+    };
     // pinned host words: [0] n_isects (sentinel -1 until the count has run), [1] the longest tile list (written first)
     // [2] which count ran (1 = tile-owner-major): the second half reads the workspace laid out by THIS choice, whatever the
     // environment switches say by then
@@ -485,43 +524,31 @@ isect_fused_begin(const Tensor &means2d, const Tensor &radii, const Tensor &dept
     Tensor offsets = at::empty({I * tile_w * tile_h}, means2d.options().dtype(at::kInt));
     if (binned_path) { // tile-owner-major path (csrc/isect_binned.hip)
         Tensor count_ws = bytes(gsx_isect_binned_count_workspace_bytes(rows, uI, utw, uth), means2d);
-        { Timed timed_("gsx_isect_binned_count", L.stream); check(gsx_isect_binned_count(fp(means2d), cp<int32_t>(radii), fp(depths), fp(conics), fp(opac), nullptr, rows, uI, uts,
+        { Timed timed_("gsx_isect_binned_count", L.stream); check(gsx_isect_binned_count(fp(means2d), cp<int32_t>(radii), fp(depths), fp(conics), fp(opac), mask_ptr(tile_mask), rows, uI, uts,
                                      utw, uth, mp<int32_t>(tiles_per_gauss), mp<int32_t>(offsets), host_total.mutable_data_ptr<int64_t>(),
                                      host_total.mutable_data_ptr<int64_t>() + 1, count_ws.mutable_data_ptr(), count_ws.numel(), L.stream),
               "gsx_isect_binned_count"); }
-        return {tiles_per_gauss, offsets, count_ws, host_total};
+        return result(offsets, count_ws, host_total);
     }
     Tensor count_ws = bytes(gsx_isect_fused_count_workspace_bytes(rows, uI, utw, uth), means2d);
-    { Timed timed_("gsx_isect_fused_count", L.stream); check(gsx_isect_fused_count(fp(means2d), cp<int32_t>(radii), fp(conics), fp(opac), nullptr, rows, uI, uts, utw, uth,
+    { Timed timed_("gsx_isect_fused_count", L.stream); check(gsx_isect_fused_count(fp(means2d), cp<int32_t>(radii), fp(conics), fp(opac), mask_ptr(tile_mask), rows, uI, uts, utw, uth,
                                 mp<int32_t>(tiles_per_gauss), mp<int32_t>(offsets), host_total.mutable_data_ptr<int64_t>(),
                                 host_total.mutable_data_ptr<int64_t>() + 1, count_ws.mutable_data_ptr(), count_ws.numel(), L.stream),
           "gsx_isect_fused_count"); }
-    return {tiles_per_gauss, offsets, count_ws, host_total};
+    return result(offsets, count_ws, host_total);
 }
 
 std::tuple<Tensor, Tensor>
 isect_fused_finish(const Tensor &means2d, const Tensor &radii, const Tensor &depths, const OptTensor &conics, const OptTensor &opac,
-                   int64_t rows, int64_t I, int64_t tile_size, int64_t tile_w, int64_t tile_h, Tensor count_ws,
-                   const Tensor &offsets, const Tensor &host_total, Tensor tiles_per_gauss)
+                   const OptTensor &tile_mask, int64_t rows, int64_t I, int64_t tile_size, int64_t tile_w, int64_t tile_h, Tensor count_ws,
+                   const Tensor &offsets, const Tensor &host_total, const OptTensor &tiles_per_gauss_)
 {
+    Tensor tiles_per_gauss = has(tiles_per_gauss_) ? *tiles_per_gauss_ : Tensor();
     Launch L(means2d);
     const uint32_t uI = (uint32_t)I, uts = (uint32_t)tile_size, utw = (uint32_t)tile_w, uth = (uint32_t)tile_h;
     volatile const int64_t *slot = host_total.const_data_ptr<int64_t>();
     auto hip_stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(means2d.device().index());
-    int64_t M = -1;
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint64_t spin = 0;; ++spin) {
-            M = *slot;
-            if (M != -1 && M == *slot) break; // two equal reads: a value caught half-written cannot pass
-            if ((spin & 63u) == 63u) std::this_thread::yield(); // the wait is ~10-100 us: do not pin a core at 100 % for it
-            if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
-                hip_stream.synchronize();
-                M = *slot;
-                break;
-            }
-        }
-    }
+    int64_t M = poll_host_word(slot, [](int64_t v) { return v == -1; }, hip_stream, std::chrono::seconds(5));
     TORCH_CHECK(host_total.numel() > 2, "isect_fused_finish: host_total must be the three pinned words of isect_fused_begin");
     bool binned = slot[2] != 0; // the choice isect_fused_begin made (never re-derived: a query here could answer differently)
     if (binned && M == GSX_ISECT_RETRY) {
@@ -530,7 +557,7 @@ isect_fused_finish(const Tensor &means2d, const Tensor &radii, const Tensor &dep
         binned   = false;
         gsx_isect_binned_note_retry(rows, uI, utw, uth);
         count_ws = bytes(gsx_isect_fused_count_workspace_bytes(rows, uI, utw, uth), means2d);
-        { Timed timed_("gsx_isect_fused_count", L.stream); check(gsx_isect_fused_count(fp(means2d), cp<int32_t>(radii), fp(conics), fp(opac), nullptr, rows, uI, uts, utw, uth,
+        { Timed timed_("gsx_isect_fused_count", L.stream); check(gsx_isect_fused_count(fp(means2d), cp<int32_t>(radii), fp(conics), fp(opac), mask_ptr(tile_mask), rows, uI, uts, utw, uth,
                                     mp<int32_t>(tiles_per_gauss), offsets.mutable_data_ptr<int32_t>(),
                                     host_total.mutable_data_ptr<int64_t>(), host_total.mutable_data_ptr<int64_t>() + 1,
                                     count_ws.mutable_data_ptr(), count_ws.numel(), L.stream),
@@ -551,7 +578,7 @@ isect_fused_finish(const Tensor &means2d, const Tensor &radii, const Tensor &dep
         return {ids, flat};
     }
     Tensor ws = bytes(gsx_isect_fused_emit_workspace_bytes(M, uI, utw, uth), means2d);
-    { Timed timed_("gsx_isect_fused_emit_sort", L.stream); check(gsx_isect_fused_emit_sort(fp(means2d), cp<int32_t>(radii), fp(depths), fp(conics), fp(opac), nullptr, rows, uI, uts,
+    { Timed timed_("gsx_isect_fused_emit_sort", L.stream); check(gsx_isect_fused_emit_sort(fp(means2d), cp<int32_t>(radii), fp(depths), fp(conics), fp(opac), mask_ptr(tile_mask), rows, uI, uts,
                                     utw, uth, count_ws.mutable_data_ptr(), count_ws.numel(), cp<int32_t>(offsets), M,
                                     mp<int64_t>(ids), mp<int32_t>(flat), ws.mutable_data_ptr(), ws.numel(), L.stream),
           "gsx_isect_fused_emit_sort"); }
@@ -634,36 +661,21 @@ rasterize_to_pixels_2dgs(const Tensor &means2d_, const Tensor &ray_transforms_, 
 }
 
 } // namespace
-void set_long_tile_hint(int64_t longest) { g_long_tile_hint = longest; }
-void note_longest_op(const Tensor &flatten_ids, int64_t longest) { note_longest(flatten_ids, longest); }
-int64_t lookup_longest_op(const Tensor &flatten_ids) { return lookup_longest(flatten_ids); }
-void note_seg_workspace_op(const Tensor &last_ids, const Tensor &ws, int64_t n_isects, int64_t cdim, int64_t seg_len,
-                           at::TensorList inputs)
-{
-    note_seg_workspace(last_ids, ws, n_isects, cdim, seg_len, inputs);
-}
-std::optional<Tensor> lookup_seg_workspace_op(const Tensor &last_ids, int64_t n_isects, int64_t cdim, int64_t seg_len,
-                                              at::TensorList inputs)
-{
-    Tensor t = lookup_seg_workspace(last_ids, n_isects, cdim, seg_len, inputs);
-    return t.defined() ? std::optional<Tensor>(t) : std::nullopt;
-}
 } // namespace gsplat_amd
 
-// gsplat_amd/_ops.py (ctypes): the longest tile list of the intersection that the next compositing call of THIS thread consumes
-extern "C" void gsx_torch_set_long_tile_hint(int64_t longest) { gsplat_amd::set_long_tile_hint(longest); }
+// gsplat_amd/_ops.py (ctypes): the segment length the compiled compositing forward uses, for the Python backward body
+extern "C" int64_t gsx_torch_seg_len() { return gsplat_amd::seg_len_env(); }
 
 TORCH_LIBRARY(gsplat_amd, m)
 {
-    m.def("isect_fused_begin(Tensor means2d, Tensor radii, Tensor depths, Tensor? conics, Tensor? opacities, int rows, int n_images, int tile_size, "
-          "int tile_w, int tile_h, int[] out_shape) -> (Tensor, Tensor, Tensor, Tensor)");
-    m.def("isect_fused_finish(Tensor means2d, Tensor radii, Tensor depths, Tensor? conics, Tensor? opacities, int rows, int n_images, "
-          "int tile_size, int tile_w, int tile_h, Tensor count_ws, Tensor offsets, Tensor host_total, Tensor tiles_per_gauss) -> (Tensor, Tensor)");
-    // the notes, for the Python op bodies: the non-fused intersection notes its longest list, the compositing backward looks
-    // up the forward's segment workspace
+    m.def("isect_fused_begin(Tensor means2d, Tensor radii, Tensor depths, Tensor? conics, Tensor? opacities, Tensor? tile_mask, int rows, int n_images, int tile_size, "
+          "int tile_w, int tile_h, int[] out_shape) -> (Tensor?, Tensor, Tensor, Tensor)");
+    m.def("isect_fused_finish(Tensor means2d, Tensor radii, Tensor depths, Tensor? conics, Tensor? opacities, Tensor? tile_mask, int rows, int n_images, "
+          "int tile_size, int tile_w, int tile_h, Tensor count_ws, Tensor offsets, Tensor host_total, Tensor? tiles_per_gauss) -> (Tensor, Tensor)");
+    // the notes, for the Python op bodies (the compositing backward looks up the longest list and the forward's segment
+    // workspace) and for tests
     m.def("note_longest(Tensor flatten_ids, int longest) -> ()");
     m.def("lookup_longest(Tensor flatten_ids) -> int");
-    m.def("note_seg_workspace(Tensor last_ids, Tensor ws, int n_isects, int cdim, int seg_len, Tensor[] inputs) -> ()");
     m.def("lookup_seg_workspace(Tensor last_ids, int n_isects, int cdim, int seg_len, Tensor[] inputs) -> Tensor?");
 }
 
@@ -676,10 +688,9 @@ TORCH_LIBRARY_IMPL(gsplat_amd, CUDA, m)
 // the notes are keyed by storage identity: any backend (tools/dry_run.py drives the host paths with CPU tensors)
 TORCH_LIBRARY_IMPL(gsplat_amd, CompositeExplicitAutograd, m)
 {
-    m.impl("note_longest", &gsplat_amd::note_longest_op);
-    m.impl("lookup_longest", &gsplat_amd::lookup_longest_op);
-    m.impl("note_seg_workspace", &gsplat_amd::note_seg_workspace_op);
-    m.impl("lookup_seg_workspace", &gsplat_amd::lookup_seg_workspace_op);
+    m.impl("note_longest", &gsplat_amd::note_longest);
+    m.impl("lookup_longest", &gsplat_amd::lookup_longest);
+    m.impl("lookup_seg_workspace", &gsplat_amd::lookup_seg_workspace);
 }
 
 TORCH_LIBRARY_IMPL(gsplat, CUDA, m)

@@ -36,8 +36,6 @@ from ._wrapper import (
     spherical_harmonics,
 )
 
-from ._ops import isect_max_tile_len as _isect_max_tile_len
-
 _COLOR_MODES = ("RGB", "RGB+D", "RGB+ED")
 _DEPTH_MODES = ("D", "ED", "RGB+D", "RGB+ED")
 _HIT_MODES = ("d", "Ed", "RGB-d", "RGB-Ed")
@@ -308,7 +306,6 @@ def rasterization(
         tiles_per_gauss, isect_ids, flatten_ids = _ops.intersect_tile_lidar(
             lidar_coeffs, means2d.contiguous(), radii.contiguous(), depths.contiguous(), None, None, None, True, segmented)
         isect_offsets = isect_offset_encode(isect_ids, I, tile_width, tile_height)
-        longest_list = 0
     else:
         if isect_pending is None:
             isect_pending = isect_tiles_begin(
@@ -320,9 +317,8 @@ def rasterization(
             isect_offsets = isect_pending.offsets
         else:
             isect_offsets = isect_offset_encode(isect_ids, I, tile_width, tile_height)
-        # the intersection also reports its longest tile list (same host words as n_isects): long lists are composited in
-        # segments (csrc/raster3d_seg.hip); 0 when the path taken does not report it
-        longest_list = _isect_max_tile_len(isect_pending)
+        # the intersection also noted its longest tile list for flatten_ids: the compositing ops cut long lists into
+        # segments (csrc/raster3d_seg.hip)
     isect_offsets = isect_offsets.reshape(batch_dims + (C, tile_height, tile_width))
 
     # ---- feature rows still in flight (distributed, dense): needed from here on -----------------------
@@ -352,7 +348,7 @@ def rasterization(
             bg = None if backgrounds is None else backgrounds[..., s:e].contiguous()
             c_, a_ = rasterize_to_pixels(means2d, conics, feats[..., s:e].contiguous(), proj_opacities, width, height,
                                          tile_size, isect_offsets, flatten_ids, backgrounds=bg, packed=packed,
-                                         absgrad=absgrad, _longest_tile_list=longest_list)
+                                         absgrad=absgrad)
             rc.append(c_)
             if ra is None:
                 ra = a_
@@ -373,7 +369,7 @@ def rasterization(
         else:
             render_colors, render_alphas = rasterize_to_pixels(
                 means2d, conics, feats, proj_opacities, width, height, tile_size, isect_offsets, flatten_ids,
-                backgrounds=backgrounds, packed=packed, absgrad=absgrad, _longest_tile_list=longest_list)
+                backgrounds=backgrounds, packed=packed, absgrad=absgrad)
 
     # ---- post-process: split extra signals, normalise expected depth ------------------------------
     render_extra = None

@@ -3,7 +3,13 @@ lists, which the other suites pin to the oracle - and against the oracle directl
 (no pixel saturates: every slice contributes), opaque ones (early termination fires inside the first slices: the later ones
 carry transmittance 0 and stop at once), a mix, backgrounds, tile masks, more than 32 channels (two channel chunks),
 several images. The backward (per-slice state from the forward's workspace, or pre-pass + per-pixel prefix, then slices walked
-back to front) against the per-tile backward."""
+back to front) against the per-tile backward.
+
+Which side runs is decided by the note that the intersection leaves for its flatten_ids (torch.ops.gsplat_amd.note_longest /
+lookup_longest: the only channel for the longest tile list). Every `fl` here comes from G.isect_tiles, so its true longest
+list is noted and the plain call is the "seg" side; the "tile" side notes -1 for the same tensor (`_per_tile`: a noted value
+below 0 means one workgroup per tile whatever the lists look like) and puts the intersection's value back afterwards."""
+import contextlib
 import math
 
 import pytest
@@ -24,6 +30,18 @@ def G():
     return gsplat_amd
 
 
+@contextlib.contextmanager
+def _per_tile(fl, longest, on=True):
+    """The compositing calls inside take one workgroup per tile for the lists `fl` (not with on=False: the plain call)."""
+    if on:
+        torch.ops.gsplat_amd.note_longest(fl, -1)
+    try:
+        yield
+    finally:
+        if on:
+            torch.ops.gsplat_amd.note_longest(fl, longest)  # what the intersection had noted
+
+
 def _lists(G, N, C, W, H, opacity, seed, shrink=0.25):
     """Projected scene squeezed into the image centre so that tile lists run to several thousand entries."""
     sc, W, H = make_scene(N=N, C=C, width=W, height=H, seed=seed)
@@ -42,6 +60,7 @@ def _lists(G, N, C, W, H, opacity, seed, shrink=0.25):
 
     # the scene must really take the segment path: its longest list is an outlier by the library's own rule
     assert int(counts.max()) > _ops._seg_cut(fl.numel(), C, tw, th), (int(counts.max()), _ops._seg_cut(fl.numel(), C, tw, th))
+    assert torch.ops.gsplat_amd.lookup_longest(fl) == int(counts.max())  # ... and the intersection noted exactly that
     return m2, con, op, off, fl, int(counts.max()), W, H, tw, th
 
 
@@ -57,8 +76,9 @@ def test_segmented_forward_matches_per_tile_walk(G, kind, D):
     masks = torch.ones(2, th, tw, dtype=torch.bool, device=DEV)
     masks[0, th // 2, tw // 2] = False  # a masked tile in the crowded centre
     for kw in (dict(), dict(backgrounds=bg), dict(backgrounds=bg, masks=masks)):
-        ref_c, ref_a = G.rasterize_to_pixels(m2, con, colors, op, W, H, 16, off, fl, _longest_tile_list=-1, **kw)  # per tile
-        seg_c, seg_a = G.rasterize_to_pixels(m2, con, colors, op, W, H, 16, off, fl, _longest_tile_list=longest, **kw)
+        with _per_tile(fl, longest):
+            ref_c, ref_a = G.rasterize_to_pixels(m2, con, colors, op, W, H, 16, off, fl, **kw)
+        seg_c, seg_a = G.rasterize_to_pixels(m2, con, colors, op, W, H, 16, off, fl, **kw)
         # the two differ only in the association order of the transmittance products (and, on saturating tiles, not at all)
         assert_close_ratio(seg_c.cpu(), ref_c.cpu(), 2e-5, 2e-6, max_bad_ratio=1e-5, name=f"{kind} colours {sorted(kw)}")
         assert_close_ratio(seg_a.cpu(), ref_a.cpu(), 2e-5, 2e-6, max_bad_ratio=1e-5, name=f"{kind} alphas {sorted(kw)}")
@@ -71,13 +91,10 @@ def test_segmented_forward_last_ids_and_oracle(G):
     m2, con, op, off, fl, longest, W, H, tw, th = _lists(G, 30000, 1, 256, 160, 0.01, seed=5)
     assert longest > 2500
     colors = torch.rand(m2.shape[:-1] + (3,), generator=torch.Generator().manual_seed(1)).to(DEV)
-    from gsplat_amd import _ops
-
     outs = {}
-    for name, hint in (("tile", -1), ("seg", longest)):  # -1: per tile, whatever the intersection noted
-        _ops.set_long_tile_hint(hint)
-        outs[name] = torch.ops.gsplat.rasterize_to_pixels_3dgs(m2, con, colors, op, None, None, W, H, 16, off, fl, False, False)
-        _ops.set_long_tile_hint(0)
+    for name in ("tile", "seg"):
+        with _per_tile(fl, longest, on=(name == "tile")):
+            outs[name] = torch.ops.gsplat.rasterize_to_pixels_3dgs(m2, con, colors, op, None, None, W, H, 16, off, fl, False, False)
     assert torch.equal(outs["seg"][3], outs["tile"][3]), "last_ids differ"
     cpu = lambda t: t.detach().cpu()  # noqa: E731
     rc_o, ra_o = O.rasterize_to_pixels(cpu(m2), cpu(con), cpu(colors), cpu(op), W, H, 16, cpu(off), cpu(fl))[:2]
@@ -100,14 +117,15 @@ def test_segmented_backward_matches_per_tile_walk(G, kind, D):
     w_a = torch.randn(2, H, W, 1, generator=g).to(DEV)
     for kw in (dict(), dict(backgrounds=bg, masks=masks)):
         grads = {}
-        for name, hint in (("tile", -1), ("seg", longest)):  # -1: per tile, whatever the intersection noted
+        for name in ("tile", "seg"):
             leaves = [t.detach().clone().requires_grad_(True) for t in (m2, con, colors, op)]
             extra = dict(kw)
             if "backgrounds" in extra:
                 extra["backgrounds"] = bg.detach().clone().requires_grad_(True)
                 leaves.append(extra["backgrounds"])
-            rc, ra = G.rasterize_to_pixels(*leaves[:4], W, H, 16, off, fl, _longest_tile_list=hint, **extra)
-            ((rc * w_c).sum() + (ra * w_a).sum()).backward()
+            with _per_tile(fl, longest, on=(name == "tile")):
+                rc, ra = G.rasterize_to_pixels(*leaves[:4], W, H, 16, off, fl, **extra)
+            ((rc * w_c).sum() + (ra * w_a).sum()).backward()  # cuts as the forward did: it kept what it had looked up
             grads[name] = [t.grad.cpu() for t in leaves]
         for nm, a, b in zip(("means2d", "conics", "colors", "opacities", "backgrounds"), grads["seg"], grads["tile"]):
             # same sums in another association order (float atomics make either side run-to-run noisy at this level too)
@@ -115,8 +133,8 @@ def test_segmented_backward_matches_per_tile_walk(G, kind, D):
 
 
 def test_segmented_backward_through_rasterization(G):
-    """rendering.py hands the intersection's longest list to forward AND backward; the per-tile side of the comparison
-    is the same call with that report suppressed."""
+    """Under rasterization() the intersection's note reaches forward AND backward; the per-tile side of the comparison
+    is the same call with -1 noted over it between the intersection and the compositing."""
     from gsplat_amd import rendering
 
     sc, W, H = make_scene(N=30000, C=1, width=256, height=160, seed=9)
@@ -126,9 +144,21 @@ def test_segmented_backward_through_rasterization(G):
     names = ("means", "quats", "scales", "opacities", "colors")
     out = {}
     seen = []
-    saved = rendering._isect_max_tile_len
+    saved = rendering.isect_tiles_finish
+    note, lookup = torch.ops.gsplat_amd.note_longest, torch.ops.gsplat_amd.lookup_longest
+
+    def finish(mode):
+        def wrapped(pending):
+            res = saved(pending)
+            if mode == "seg":
+                seen.append(lookup(res[2]))
+            else:
+                note(res[2], -1)
+            return res
+        return wrapped
+
     for mode in ("seg", "tile"):
-        rendering._isect_max_tile_len = (lambda st: seen.append(saved(st)) or seen[-1]) if mode == "seg" else (lambda st: -1)
+        rendering.isect_tiles_finish = finish(mode)
         try:
             leaves = {k: a[k].detach().clone().requires_grad_(True) for k in names}
             rc, ra, info = G.rasterization(leaves["means"], leaves["quats"], leaves["scales"], leaves["opacities"], leaves["colors"],
@@ -136,7 +166,7 @@ def test_segmented_backward_through_rasterization(G):
             (rc.square().sum() + ra.sum()).backward()
             out[mode] = (rc.detach().cpu(), [leaves[k].grad.cpu() for k in names])
         finally:
-            rendering._isect_max_tile_len = saved
+            rendering.isect_tiles_finish = saved
     assert seen and seen[0] > 2500, seen  # the segment path really ran
     assert_close_ratio(out["seg"][0], out["tile"][0], 2e-5, 2e-6, max_bad_ratio=1e-5, name="render")
     for nm, x, y in zip(names, out["seg"][1], out["tile"][1]):
@@ -145,7 +175,7 @@ def test_segmented_backward_through_rasterization(G):
 
 def test_uniformly_long_lists_stay_on_the_per_tile_walk(G):
     """Segments are for outliers: when EVERY list is long (the c4 regime) the cut moves up with the mean and the plain
-    entries run - bit-identical results with and without the hint."""
+    entries run - bit-identical results with the intersection's note and with -1 noted over it."""
     from gsplat_amd import _ops
 
     sc, W, H = make_scene(N=60000, C=1, width=64, height=64, seed=3, scale_range=(0.05, 0.2))
@@ -160,9 +190,11 @@ def test_uniformly_long_lists_stay_on_the_per_tile_walk(G):
     longest = int(counts.max())
     assert longest > _ops.SEG_MIN_LONGEST and longest <= _ops._seg_cut(fl.numel(), 1, 4, 4), (longest, fl.numel())
     colors = torch.rand(m2.shape[:-1] + (3,), generator=torch.Generator().manual_seed(1)).to(DEV)
-    ref = G.rasterize_to_pixels(m2, con, colors, op, W, H, 16, off, fl, _longest_tile_list=-1)
-    hinted = G.rasterize_to_pixels(m2, con, colors, op, W, H, 16, off, fl, _longest_tile_list=longest)
-    assert torch.equal(ref[0], hinted[0]) and torch.equal(ref[1], hinted[1])
+    assert torch.ops.gsplat_amd.lookup_longest(fl) == longest
+    with _per_tile(fl, longest):
+        ref = G.rasterize_to_pixels(m2, con, colors, op, W, H, 16, off, fl)
+    noted = G.rasterize_to_pixels(m2, con, colors, op, W, H, 16, off, fl)
+    assert torch.equal(ref[0], noted[0]) and torch.equal(ref[1], noted[1])
 
 
 @pytest.mark.parametrize("case", ["absgrad", "five_channels", "tile8"])
@@ -174,7 +206,7 @@ def test_segment_hint_with_backward_fallbacks(G, case):
     D = 5 if case == "five_channels" else 3
     ts = 16
     if case == "tile8":
-        # tile size 8 needs its own lists; the hint is then above the cut of THAT grid or not - either way results must agree
+        # tile size 8 needs its own lists; the note is then above the cut of THAT grid or not - either way results must agree
         ts = 8
         sc, _, _ = make_scene(N=40000, C=1, width=W, height=H, seed=31)
         a = {k: v.to(DEV) for k, v in sc.items()}
@@ -192,9 +224,10 @@ def test_segment_hint_with_backward_fallbacks(G, case):
     colors = torch.rand(m2.shape[:-1] + (D,), generator=g).to(DEV)
     w_c = torch.randn(1, H, W, D, generator=g).to(DEV)
     grads = {}
-    for name, hint in (("tile", -1), ("seg", longest)):  # -1: per tile, whatever the intersection noted
+    for name in ("tile", "seg"):
         leaves = [t.detach().clone().requires_grad_(True) for t in (m2, con, colors, op)]
-        rc, ra = G.rasterize_to_pixels(*leaves, W, H, ts, off, fl, absgrad=(case == "absgrad"), _longest_tile_list=hint)
+        with _per_tile(fl, longest, on=(name == "tile")):
+            rc, ra = G.rasterize_to_pixels(*leaves, W, H, ts, off, fl, absgrad=(case == "absgrad"))
         ((rc * w_c).sum() + ra.sum()).backward()
         grads[name] = [t.grad.cpu() for t in leaves] + ([leaves[0].absgrad.cpu()] if case == "absgrad" else [])
     for nm, x, y in zip(("means2d", "conics", "colors", "opacities", "absgrad"), grads["seg"], grads["tile"]):
@@ -204,14 +237,18 @@ def test_segment_hint_with_backward_fallbacks(G, case):
 def test_stage_level_callers_get_segments_without_a_hint(G):
     """isect_tiles -> isect_offset_encode -> rasterize_to_pixels driven by hand (the reference's stage API, no rasterization()
     in between): the intersection notes the longest list of its result under flatten_ids, the compositing ops look it up -
-    forward AND backward take the segment kernels, bit-identical to the explicitly hinted call and not to the per-tile walk."""
+    forward AND backward take the segment kernels, bit-identical to the call with `longest` noted by hand ("hinted") and not
+    to the per-tile walk."""
     m2, con, op, off, fl, longest, W, H, tw, th = _lists(G, 40000, 1, 320, 192, 0.01, seed=41)
     colors = torch.rand(m2.shape[:-1] + (3,), generator=torch.Generator().manual_seed(2)).to(DEV)
     w_c = torch.randn(1, H, W, 3, generator=torch.Generator().manual_seed(3)).to(DEV)
     res = {}
-    for name, kw in (("noted", {}), ("hinted", dict(_longest_tile_list=longest)), ("tile", dict(_longest_tile_list=-1))):
+    for name in ("noted", "hinted", "tile"):
         leaves = [t.detach().clone().requires_grad_(True) for t in (m2, con, colors, op)]
-        rc, ra = G.rasterize_to_pixels(*leaves, W, H, 16, off, fl, **kw)
+        if name == "hinted":
+            torch.ops.gsplat_amd.note_longest(fl, longest)  # noting again replaces the intersection's note (same value)
+        with _per_tile(fl, longest, on=(name == "tile")):
+            rc, ra = G.rasterize_to_pixels(*leaves, W, H, 16, off, fl)
         ((rc * w_c).sum() + ra.sum()).backward()
         res[name] = [rc.detach(), ra.detach()] + [t.grad for t in leaves]
     assert all(torch.equal(a, b) for a, b in zip(res["noted"][:2], res["hinted"][:2])), "forward did not take the segments"
@@ -239,9 +276,7 @@ def test_segmented_backward_from_the_forward_workspace_equals_the_prepass(G, kin
     bg = torch.rand(2, 3, generator=g).to(DEV)
     w_c = torch.randn(2, H, W, 3, generator=g).to(DEV)
     w_a = torch.randn(2, H, W, 1, generator=g).to(DEV)
-    _ops.set_long_tile_hint(longest)
     rc, ra, _, last_ids = torch.ops.gsplat.rasterize_to_pixels_3dgs(m2, con, colors, op, bg, None, W, H, 16, off, fl, False, False)
-    _ops.set_long_tile_hint(0)
     ins = [m2, con, colors, op, off, fl]
     lookup = torch.ops.gsplat_amd.lookup_seg_workspace
     noted = lookup(last_ids, fl.numel(), 3, _ops.SEG_LEN, ins)
@@ -252,20 +287,14 @@ def test_segmented_backward_from_the_forward_workspace_equals_the_prepass(G, kin
     assert lookup(last_ids, fl.numel(), 3, _ops.SEG_LEN, [m2, con, colors.clone(), op, off, fl]) is None
     op.mul_(1.0)
     assert lookup(last_ids, fl.numel(), 3, _ops.SEG_LEN, ins) is None, "an input was written to after the forward"
-    _ops.set_long_tile_hint(longest)
     rc, ra, _, last_ids = torch.ops.gsplat.rasterize_to_pixels_3dgs(m2, con, colors, op, bg, None, W, H, 16, off, fl, False, False)
-    _ops.set_long_tile_hint(0)
     noted = lookup(last_ids, fl.numel(), 3, _ops.SEG_LEN, ins)
     assert noted is not None
     before = noted.clone()
 
     def backward(li):
-        _ops.set_long_tile_hint(longest)
-        try:
-            return torch.ops.gsplat.rasterize_to_pixels_3dgs_bwd(m2, con, colors, op, bg, None, off, fl, ra, li, W, H, 16, False,
-                                                                 w_c, w_a, True)
-        finally:
-            _ops.set_long_tile_hint(0)
+        return torch.ops.gsplat.rasterize_to_pixels_3dgs_bwd(m2, con, colors, op, bg, None, off, fl, ra, li, W, H, 16, False,
+                                                             w_c, w_a, True)
 
     reuse, again, prepass = backward(last_ids), backward(last_ids), backward(last_ids.clone())
     assert torch.equal(noted, before), "the backward wrote into the forward's workspace"

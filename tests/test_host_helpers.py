@@ -178,3 +178,32 @@ def test_intersection_path_memory_is_per_caller_and_per_thread():
     assert seen == [1]  # another thread has its own default
     skipped = sum(1 for _ in range(70) if L.gsx_isect_binned_should_try(*shape, 0) == 0)
     assert skipped == 63  # 63 intersections skip the attempt, the 64th probes again
+
+
+def test_longest_list_notes_are_keyed_by_tensor_identity_and_expired_slots_go_first():
+    """torch.ops.gsplat_amd.note_longest / lookup_longest (csrc/torch_ops.cpp): the only channel that carries an intersection's
+    longest tile list to the compositing ops. Keyed by the identity of the tensor (storage, offset, length), 16 slots; a fresh
+    note takes the slot of a tensor that has died before it takes the oldest one."""
+    import gsplat_amd  # noqa: F401  (loads the library that defines the ops)
+
+    note, lookup = torch.ops.gsplat_amd.note_longest, torch.ops.gsplat_amd.lookup_longest
+    fl = torch.arange(10, dtype=torch.int32)
+    assert lookup(fl) == 0  # nothing noted
+    note(fl, 4321)
+    assert lookup(fl) == 4321
+    assert lookup(fl.clone()) == 0  # same values, another storage
+    assert lookup(fl[1:]) == 0 and lookup(fl[:9]) == 0  # views at another offset / of another length
+    assert lookup(fl[:]) == 4321 and lookup(fl.view(2, 5)) == 4321  # the same elements of the same storage
+    note(fl, 77)  # noting again replaces
+    assert lookup(fl) == 77
+    note(fl, -1)  # below 0 (one workgroup per tile, whatever the lists look like) comes back as it is
+    assert lookup(fl) == -1
+    del fl  # its slot is free now, and goes before any live tensor's
+    live = [torch.zeros(3, dtype=torch.int32) for _ in range(16)]
+    for i, t in enumerate(live):
+        note(t, 100 + i)
+    assert [lookup(t) for t in live] == [100 + i for i in range(16)]  # none of the 16 pushed another one out
+    extra = torch.zeros(3, dtype=torch.int32)
+    note(extra, 999)  # 17 live tensors: the oldest note goes
+    assert lookup(extra) == 999 and lookup(live[0]) == 0
+    assert [lookup(t) for t in live[1:]] == [101 + i for i in range(15)]
