@@ -44,6 +44,23 @@ __device__ __forceinline__ float load_vc(const ShArgs &a, int64_t row, uint32_t 
     return (a.post_colors && !(a.post_colors[row * a.D + ch] > 0.0f)) ? 0.0f : v;
 }
 
+// The three colour cotangents of `row`, the cotangent tested first: a channel that is zero never reads post_colors. false = the
+// row is dead for the backward (masked, off screen, or every channel compares equal to zero after the clamp cut; NaN is live):
+// it contributes nothing to any gradient, and vc is +0.
+__device__ __forceinline__ bool load_vc3(const ShArgs &a, int64_t row, float *vc)
+{
+    vc[0] = vc[1] = vc[2] = 0.0f;
+    if (row_dead(a, row)) return false;
+    const float *v = a.v_colors + row * a.vc_stride;
+    const float v0 = v[0], v1 = v[1], v2 = v[2];
+    if (v0 == 0.0f && v1 == 0.0f && v2 == 0.0f) return false;
+    const float *pc = a.post_colors ? a.post_colors + row * 3 : nullptr;
+    if (v0 != 0.0f && !(pc && !(pc[0] > 0.0f))) vc[0] = v0;
+    if (v1 != 0.0f && !(pc && !(pc[1] > 0.0f))) vc[1] = v1;
+    if (v2 != 0.0f && !(pc && !(pc[2] > 0.0f))) vc[2] = v2;
+    return vc[0] != 0.0f || vc[1] != 0.0f || vc[2] != 0.0f;
+}
+
 // generic kernels: accumulate one (row, channel) contribution to d(loss)/d(dir) into v_means[b,g] and / or v_dirs[row]
 __device__ __forceinline__ void add_v_dir(const ShArgs &a, int64_t row, uint32_t b, uint32_t g, float vx, float vy, float vz)
 {
@@ -503,11 +520,11 @@ __global__ void __launch_bounds__(256) sh3_bwd_packed_kernel(const ShArgs a)
     float vco[NF];
 #pragma unroll
     for (int i = 0; i < NF; ++i) vco[i] = 0.0f;
-    if (row_dead(a, row)) {
+    float vc[3];
+    if (!load_vc3(a, row, vc)) { // nothing to add anywhere (v_means, v_dirs and scattered v_coeffs are zero-initialised)
         if (a.coeffs_gathered) store_row<NF>(out, vec, vco, a.K * 3, true);
         return;
     }
-    const float vc[3] = {load_vc(a, row, 0), load_vc(a, row, 1), load_vc(a, row, 2)};
     float v_dir[3] = {0.f, 0.f, 0.f};
     sh3_row_vjp<DEG, WANT_MEANS>(a, b, c, g, crow, vc, vec, vco, v_dir);
     if (a.coeffs_gathered) store_row<NF>(out, vec, vco, a.K * 3, true);
@@ -552,8 +569,8 @@ __global__ void __launch_bounds__(256) sh3_bwd_dense_kernel(const ShArgs a)
                 row = a.row_map[row];
                 if (row < 0) continue;
             }
-            if (row_dead(a, row)) continue;
-            const float vc[3] = {load_vc(a, row, 0), load_vc(a, row, 1), load_vc(a, row, 2)};
+            float vc[3];
+            if (!load_vc3(a, row, vc)) continue;
             float vd[3] = {0.f, 0.f, 0.f};
             sh3_row_vjp<DEG, WANT_MEANS>(a, b, c, g, (int64_t)g, vc, vec, vco, vd);
             v_dir[0] += vd[0]; v_dir[1] += vd[1]; v_dir[2] += vd[2];
@@ -599,15 +616,19 @@ sh3_bwd_tiled_kernel(const ShArgs a)
     const uint32_t row_q = a.K * 3u / 4u;
     const uint32_t n_img = MULTI ? a.B * a.C : 1u;
 
+    // Liveness first, per row: a Gaussian that no image gives a non-zero colour cotangent (occluded behind the compositing cut,
+    // off screen, masked) reads neither its coefficient row nor its mean, and its gradient rows are +0. vc = the cotangent of
+    // the first live row (!MULTI: of the only row, kept for the walk below).
+    float vc[3] = {0.f, 0.f, 0.f};
+    bool any = false;
+    if (have)
+        for (uint32_t i = 0; i < n_img && !any; ++i) {
+            int64_t row = (int64_t)i * a.N + g;
+            if (a.row_map) row = a.row_map[row];
+            any = row >= 0 && load_vc3(a, row, vc);
+        }
     if constexpr (WANT_MEANS) {
         // the coefficient row is needed (for d/d mean) iff the Gaussian is live in some image
-        bool any = false;
-        if (have)
-            for (uint32_t i = 0; i < n_img && !any; ++i) {
-                int64_t row = (int64_t)i * a.N + g;
-                if (a.row_map) row = a.row_map[row];
-                any = row >= 0 && !row_dead(a, row);
-            }
         const uint64_t any_mask = __builtin_amdgcn_ballot_w64(any);
         if (any_mask) {
             tile_load<NF>(a.coeffs + block0, row_q, any_mask, tile, lane);
@@ -617,19 +638,17 @@ sh3_bwd_tiled_kernel(const ShArgs a)
     float vco[MULTI ? NF : 1];
 #pragma unroll
     for (int i = 0; i < (MULTI ? NF : 1); ++i) vco[i] = 0.0f;
-    float Y[NB], vc[3] = {0.f, 0.f, 0.f}; // !MULTI: the live row's basis and cotangent, for the outer product at the end
+    float Y[NB]; // !MULTI: the live row's basis, for the outer product with its cotangent at the end
 #pragma unroll
     for (int k = 0; k < NB; ++k) Y[k] = 0.0f;
     for (uint32_t b = 0; have && b < (MULTI ? a.B : 1u); ++b) {
         float v_dir[3] = {0.f, 0.f, 0.f};
-        for (uint32_t c = 0; c < (MULTI ? a.C : 1u); ++c) {
+        for (uint32_t c = 0; any && c < (MULTI ? a.C : 1u); ++c) {
             int64_t row = ((int64_t)b * a.C + c) * a.N + g;
-            if (a.row_map) {
-                row = a.row_map[row];
-                if (row < 0) continue;
+            if (a.row_map) row = a.row_map[row]; // !MULTI: `any` says it is there
+            if constexpr (MULTI) {
+                if (row < 0 || !load_vc3(a, row, vc)) continue;
             }
-            if (row_dead(a, row)) continue;
-            vc[0] = load_vc(a, row, 0); vc[1] = load_vc(a, row, 1); vc[2] = load_vc(a, row, 2);
             float d[3];
             view_dir(a, b, c, g, d);
             const float inv = safe_inv_norm(d);
@@ -687,7 +706,7 @@ sh3_bwd_tiled_kernel(const ShArgs a)
         for (int j = 0; j < 4; ++j) {
             const int f = 4 * i + j;
             if constexpr (MULTI) v[j] = f < NF ? vco[f < NF ? f : 0] : 0.0f;
-            else v[j] = f < NF ? Y[(f < NF ? f : 0) / 3] * vc[f % 3] : 0.0f; // no live row: vc = 0
+            else v[j] = f < NF ? Y[(f < NF ? f : 0) / 3] * vc[f % 3] : 0.0f; // no live row: Y = vc = +0
         }
         mine[i] = v;
     }
