@@ -278,6 +278,14 @@ def kmeans_workspace_bytes(n: int, d: int, k: int) -> int:
     return int(_lib.gsx_kmeans_workspace_bytes(n, d, k))
 
 
+def plas_workspace_bytes(h: int, w: int, c: int) -> int:
+    return int(_lib.gsx_plas_workspace_bytes(h, w, c))
+
+
+def plas_partials_floats(h: int, w: int) -> int:
+    return int(_lib.gsx_plas_partials_floats(h, w))
+
+
 def tile_sort_supported(n_images: int, tile_w: int, tile_h: int) -> bool:
     return bool(_lib.gsx_isect_tile_sort_supported(n_images, tile_w, tile_h))
 

@@ -10,7 +10,8 @@ directory written here decompresses with the reference and the other way round. 
 
 What this module does not take from the reference are its three third-party dependencies, none of which is in this image:
 ``imageio`` -> the PNG codec in ``_png.py``; ``torchpq.clustering.KMeans`` -> ``kmeans_l1`` below (Lloyd's iteration with
-L1 assignment: the kernels of csrc/kmeans.hip on the GPU, a chunked torch composition elsewhere); ``plas`` -> see ``sort.py``.
+L1 assignment: the kernels of csrc/kmeans.hip on the GPU, a chunked torch composition elsewhere); ``plas`` -> ``sort.plas_sort``
+(a block-assignment grid sort: the kernels of csrc/plas.hip on the GPU; on the CPU the default stays the Morton layout of ``sort.py``).
 """
 from __future__ import annotations
 
@@ -298,10 +299,12 @@ class PngCompression:
     "sh0", "shN", plus any extra fields (stored as .npz) - into a directory (reference PngCompression, :30-147).
 
     The number of splats must be a perfect square to fill the images: otherwise the lowest-opacity splats are dropped (and
-    a warning printed), like the reference. ``use_sort`` orders the splats for compressibility first (``sort.py``)."""
+    a warning printed), like the reference. ``use_sort`` orders the splats for compressibility first; ``sort_method`` (not a
+    field of the reference) is ``sort_splats``' `method`: "auto", "plas" or "morton" (``sort.py``)."""
 
     use_sort: bool = True
     verbose: bool = True
+    sort_method: str = "auto"
 
     def compress(self, compress_dir: str, splats: Dict[str, Tensor]) -> None:
         os.makedirs(compress_dir, exist_ok=True)
@@ -316,7 +319,7 @@ class PngCompression:
             splats = {k: v[keep] for k, v in splats.items()}
             print(f"Warning: Number of Gaussians was not square. Removed {surplus} Gaussians.")
         if self.use_sort:
-            splats = sort_splats(splats, verbose=self.verbose)
+            splats = sort_splats(splats, verbose=self.verbose, method=self.sort_method)
         meta = {}
         for name, params in splats.items():
             meta[name] = _CODECS.get(name, _Npz).compress(compress_dir, name, params, side=side, verbose=self.verbose)

@@ -1142,6 +1142,29 @@ int64_t gsx_kmeans_workspace_bytes(int64_t N, uint32_t D, int64_t K);
 int gsx_kmeans_update(const float *x, int64_t N, uint32_t D, const int32_t *labels, const int64_t *sorted_keys, int64_t K,
                       const float *centroids_in, float *centroids_out, int32_t *counts, float *shift, void *workspace, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The native grid sort behind gsplat_amd.compression.sort.plas_sort (PngCompression's ordering; the reference imports the
+ * third-party `plas` package: gsplat/compression/sort.py:22-64). float32, grid / target [H * W, C] contiguous (cell y * W + x of
+ * an H x W grid), 1 <= C <= 32, H * W < 2^31. The torch functions of sort.py define both results.
+ *   gsx_plas_blur  target = the box mean of width 2 r + 1 along W, then along H, reflect borders without edge repeat;
+ *                  1 <= r <= min(H, W) - 1. Sliding window sums over segments of a line (no prefix sums): every output is within
+ *                  2 (max(H, W) + 2 r + 1) 2^-24 max|grid| of the exact mean. grid, target and workspace must not alias.
+ *                  workspace [gsx_plas_workspace_bytes(H, W, C)] bytes (0 for arguments outside the range).
+ *   gsx_plas_step  One assignment step, in place on grid and on index [H * W] int32. The grid is cut into b x b blocks (b a
+ *                  power of two in [2, 32768]) at an offset hashed from (seed, t); each complete block's cells are dealt into
+ *                  groups of four by a keyed bijection (sort.py: plas_groups, integer arithmetic, reproduced exactly). Per group
+ *                  with rows x_0..3 and targets t_0..3: cost[i][j] = sum_c (x_i[c] - t_j[c])^2 in float32, added in a fixed tree, product
+ *                  and sum rounded separately; of the 24 permutations in lexicographic order the lowest total
+ *                  ((cost[p0][0] + cost[p1][1]) + cost[p2][2]) + cost[p3][3] moves (row p[j] to position j), the first among
+ *                  equals: the identity wins ties. Cells outside complete blocks keep their bits. result[0] = the sum over the
+ *                  groups of total_identity - total_chosen, result[1] = of total_identity, both written on the device, added in
+ *                  a fixed order (no float atomics: bit-equal between runs). partials [gsx_plas_partials_floats(H, W)] floats. */
+int64_t gsx_plas_workspace_bytes(int64_t H, int64_t W, uint32_t C);
+int64_t gsx_plas_partials_floats(int64_t H, int64_t W);
+int gsx_plas_blur(const float *grid, int64_t H, int64_t W, uint32_t C, int64_t r, float *target, void *workspace, void *stream);
+int gsx_plas_step(float *grid, const float *target, int32_t *index, int64_t H, int64_t W, uint32_t C, uint32_t b, uint32_t seed,
+                  uint32_t t, float *partials, float *result, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
