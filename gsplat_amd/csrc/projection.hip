@@ -700,6 +700,28 @@ static int check_proj_common(const char *fn, const float *means, const float *co
 
 using namespace gsx;
 
+// ---- host side: one body per kernel family. The extern "C" entries fill the kernel's argument block and forward to it; `fn`
+// is the entry's own name, which the messages carry (the launch names drop its gsx_ prefix: fn + 4) ----
+
+// what the forward, count and write entries share; the write entries add their rows with proj_rows()
+static ProjArgs proj_args(const float *means, const float *covars, const float *quats, const float *scales,
+                          const float *opacities, const float *viewmats, const float *Ks, uint32_t B, uint32_t C, uint32_t N,
+                          uint32_t width, uint32_t height, float eps2d, float near_plane, float far_plane, float radius_clip,
+                          int camera_model, int calc_compensations)
+{
+    ProjArgs a{};
+    a.means = means; a.covars = covars; a.quats = quats; a.scales = scales; a.opacities = opacities;
+    a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N; a.width = width; a.height = height;
+    a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
+    a.camera_model = camera_model; a.calc_compensations = calc_compensations;
+    return a;
+}
+static void proj_rows(ProjArgs &a, int32_t *radii, float *means2d, float *depths, float *conics, float *compensations)
+{
+    a.radii = radii; a.means2d = means2d; a.depths = depths; a.conics = conics; a.compensations = compensations;
+    a.calc_compensations = compensations != nullptr;
+}
+
 extern "C" int gsx_project_ewa_fwd(const float *means, const float *covars, const float *quats, const float *scales,
                                    const float *opacities, const float *viewmats, const float *Ks, uint32_t B,
                                    uint32_t C, uint32_t N, uint32_t width, uint32_t height, float eps2d,
@@ -712,12 +734,9 @@ extern "C" int gsx_project_ewa_fwd(const float *means, const float *covars, cons
     int rc = check_proj_common("gsx_project_ewa_fwd", means, covars, quats, scales, viewmats, Ks, camera_model);
     if (rc != GSX_OK) return rc;
     GSX_REQUIRE(radii && means2d && depths && conics, "gsx_project_ewa_fwd: null output");
-    ProjArgs a{};
-    a.means = means; a.covars = covars; a.quats = quats; a.scales = scales; a.opacities = opacities;
-    a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N; a.width = width; a.height = height;
-    a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
-    a.camera_model = camera_model; a.calc_compensations = compensations != nullptr;
-    a.radii = radii; a.means2d = means2d; a.depths = depths; a.conics = conics; a.compensations = compensations;
+    ProjArgs a = proj_args(means, covars, quats, scales, opacities, viewmats, Ks, B, C, N, width, height, eps2d, near_plane,
+                           far_plane, radius_clip, camera_model, 0);
+    proj_rows(a, radii, means2d, depths, conics, compensations);
     if (C > 1)
         project_fwd_gaussian_major_kernel<<<dim3((uint32_t)ceil_div((int64_t)B * N, 256)), dim3(256), 0, (hipStream_t)stream>>>(a);
     else
@@ -737,11 +756,9 @@ extern "C" int gsx_project_ewa_packed_count(const float *means, const float *cov
     int rc = check_proj_common("gsx_project_ewa_packed_count", means, covars, quats, scales, viewmats, Ks, camera_model);
     if (rc != GSX_OK) return rc;
     GSX_REQUIRE(visible, "gsx_project_ewa_packed_count: null output");
-    ProjArgs a{};
-    a.means = means; a.covars = covars; a.quats = quats; a.scales = scales; a.opacities = opacities;
-    a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N; a.width = width; a.height = height;
-    a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
-    a.camera_model = camera_model; a.calc_compensations = calc_compensations; a.visible = visible;
+    ProjArgs a = proj_args(means, covars, quats, scales, opacities, viewmats, Ks, B, C, N, width, height, eps2d, near_plane,
+                           far_plane, radius_clip, camera_model, calc_compensations);
+    a.visible = visible;
     project_count_kernel<<<dim3((uint32_t)ceil_div(count, 256)), dim3(256), 0, (hipStream_t)stream>>>(a);
     return check_launch("project_ewa_packed_count");
 }
@@ -770,12 +787,9 @@ extern "C" int gsx_project_ewa_packed_write(const float *means, const float *cov
     GSX_REQUIRE(row_offsets, "gsx_project_ewa_packed_write: null row_offsets");
     GSX_REQUIRE(nnz == 0 || (batch_ids && camera_ids && gaussian_ids && radii && means2d && depths && conics),
                 "gsx_project_ewa_packed_write: null output");
-    ProjArgs a{};
-    a.means = means; a.covars = covars; a.quats = quats; a.scales = scales; a.opacities = opacities;
-    a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N; a.width = width; a.height = height;
-    a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
-    a.camera_model = camera_model; a.calc_compensations = compensations != nullptr;
-    a.radii = radii; a.means2d = means2d; a.depths = depths; a.conics = conics; a.compensations = compensations;
+    ProjArgs a = proj_args(means, covars, quats, scales, opacities, viewmats, Ks, B, C, N, width, height, eps2d, near_plane,
+                           far_plane, radius_clip, camera_model, 0);
+    proj_rows(a, radii, means2d, depths, conics, compensations);
     a.row_offsets = row_offsets; a.nnz = nnz; a.batch_ids = batch_ids; a.camera_ids = camera_ids;
     a.gaussian_ids = gaussian_ids; a.indptr = indptr;
     project_write_kernel<<<dim3((uint32_t)ceil_div(count + 1, 256)), dim3(256), 0, (hipStream_t)stream>>>(a);
@@ -803,11 +817,8 @@ extern "C" int gsx_project_ewa_packed_count_blocks(const float *means, const flo
         int rc = check_proj_common("gsx_project_ewa_packed_count_blocks", means, covars, quats, scales, viewmats, Ks, camera_model);
         if (rc != GSX_OK) return rc;
     }
-    ProjArgs a{};
-    a.means = means; a.covars = covars; a.quats = quats; a.scales = scales; a.opacities = opacities;
-    a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N; a.width = width; a.height = height;
-    a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
-    a.camera_model = camera_model; a.calc_compensations = calc_compensations;
+    const ProjArgs a = proj_args(means, covars, quats, scales, opacities, viewmats, Ks, B, C, N, width, height, eps2d, near_plane,
+                                 far_plane, radius_clip, camera_model, calc_compensations);
     PackedBlocks pb{block_counts, block_offsets};
     const uint32_t n_blocks = (uint32_t)gsx_project_packed_blocks(count);
     project_count_blocks_kernel<<<dim3(n_blocks), dim3(256), 0, (hipStream_t)stream>>>(a, pb);
@@ -842,31 +853,102 @@ extern "C" int gsx_project_ewa_packed_write_blocks(const float *means, const flo
         GSX_REQUIRE(batch_ids && camera_ids && gaussian_ids && radii && means2d && depths && conics,
                     "gsx_project_ewa_packed_write_blocks: null output");
     }
-    ProjArgs a{};
-    a.means = means; a.covars = covars; a.quats = quats; a.scales = scales; a.opacities = opacities;
-    a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N; a.width = width; a.height = height;
-    a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
-    a.camera_model = camera_model; a.calc_compensations = compensations != nullptr;
-    a.radii = radii; a.means2d = means2d; a.depths = depths; a.conics = conics; a.compensations = compensations;
+    ProjArgs a = proj_args(means, covars, quats, scales, opacities, viewmats, Ks, B, C, N, width, height, eps2d, near_plane,
+                           far_plane, radius_clip, camera_model, 0);
+    proj_rows(a, radii, means2d, depths, conics, compensations);
     a.batch_ids = batch_ids; a.camera_ids = camera_ids; a.gaussian_ids = gaussian_ids; a.indptr = indptr;
     PackedBlocks pb{nullptr, block_offsets};
     project_write_blocks_kernel<<<dim3((uint32_t)gsx_project_packed_blocks(count)), dim3(256), 0, (hipStream_t)stream>>>(a, pb);
     return check_launch("project_ewa_packed_write_blocks");
 }
 
-static void fill_bwd(ProjBwdArgs &a, const float *means, const float *covars, const float *quats, const float *scales,
-                     const float *viewmats, const float *Ks, uint32_t B, uint32_t C, uint32_t N, uint32_t width,
-                     uint32_t height, float eps2d, int camera_model, const float *conics, const float *compensations,
-                     const float *v_means2d, uint32_t m2_stride, const float *v_depths, const float *v_conics,
-                     uint32_t con_stride, const float *v_compensations, float *v_means, float *v_covars,
-                     float *v_quats, float *v_scales, float *v_viewmats)
+// the backward entries fill this block and hand it to project_bwd() / project_packed_bwd() below, which check it and launch
+static ProjBwdArgs proj_bwd_args(const float *means, const float *covars, const float *quats, const float *scales,
+                                 const float *viewmats, const float *Ks, uint32_t B, uint32_t C, uint32_t N, uint32_t width,
+                                 uint32_t height, float eps2d, int camera_model, const float *conics,
+                                 const float *compensations, const float *v_means2d, uint32_t m2_stride, const float *v_depths,
+                                 const float *v_conics, uint32_t con_stride, const float *v_compensations, float *v_means,
+                                 float *v_covars, float *v_quats, float *v_scales, float *v_viewmats)
 {
+    ProjBwdArgs a{};
     a.m2_stride = m2_stride; a.con_stride = con_stride;
     a.means = means; a.covars = covars; a.quats = quats; a.scales = scales; a.viewmats = viewmats; a.Ks = Ks;
     a.B = B; a.C = C; a.N = N; a.width = width; a.height = height; a.eps2d = eps2d; a.camera_model = camera_model;
     a.conics = conics; a.compensations = compensations; a.v_means2d = v_means2d; a.v_depths = v_depths;
     a.v_conics = v_conics; a.v_compensations = (compensations && v_compensations) ? v_compensations : nullptr;
     a.v_means = v_means; a.v_covars = v_covars; a.v_quats = v_quats; a.v_scales = v_scales; a.v_viewmats = v_viewmats;
+    return a;
+}
+
+// what every backward entry checks once it knows that there is work: the scene, its own per-pair inputs, the row strides
+static int check_proj_bwd(const char *fn, const ProjBwdArgs &a, bool packed)
+{
+    int rc = check_proj_common(fn, a.means, a.covars, a.quats, a.scales, a.viewmats, a.Ks, a.camera_model);
+    if (rc != GSX_OK) return rc;
+    GSX_REQUIRE((packed ? a.batch_ids && a.camera_ids && a.gaussian_ids : a.radii != nullptr) && a.conics && a.v_means2d
+                && a.v_conics, "%s: null input", fn);
+    GSX_REQUIRE(a.m2_stride >= 2 && a.con_stride >= 3, "%s: row strides must be >= 2 / >= 3", fn);
+    return GSX_OK;
+}
+
+// zero gradient for every Gaussian when there is no view / no row whose cotangent could reach it (the _opac entries)
+static int zero_v_opacities(const char *fn, const ProjBwdArgs &a, hipStream_t s)
+{
+    if (hipMemsetAsync(a.v_opacities, 0, (size_t)a.B * a.N * sizeof(float), s) != hipSuccess) {
+        set_last_error("%s: memset failed", fn);
+        return GSX_ERR_LAUNCH;
+    }
+    return GSX_OK;
+}
+
+// Gaussian-major: one thread per Gaussian loops over the images (dense rows, or packed rows through a.row_map); every output
+// row is written exactly once (no atomics, no zero-initialised outputs needed)
+static int launch_project_bwd(const char *fn, const ProjBwdArgs &a, hipStream_t s)
+{
+    const dim3 grid((uint32_t)ceil_div((int64_t)a.B * a.N, 256)), block(256);
+    if (a.v_viewmats) project_bwd_kernel<true><<<grid, block, 0, s>>>(a);
+    else project_bwd_kernel<false><<<grid, block, 0, s>>>(a);
+    return check_launch(fn + 4);
+}
+
+// gsx_project_ewa_bwd and, with `opac`, gsx_project_ewa_bwd_opac
+static int project_bwd(const char *fn, const ProjBwdArgs &a, bool opac, hipStream_t s)
+{
+    const int64_t count = (int64_t)a.B * a.N;
+    if (count == 0 || (!opac && a.C == 0)) return GSX_OK;
+    if (opac) {
+        GSX_REQUIRE(a.v_opacities, "%s: null v_opacities", fn);
+        if (a.C == 0) return zero_v_opacities(fn, a, s); // no views: the cotangent is empty
+        GSX_REQUIRE(a.v_view_opacities && a.opac_stride >= 1, "%s: null opacity cotangent", fn);
+    }
+    int rc = check_proj_bwd(fn, a, false);
+    if (rc != GSX_OK) return rc;
+    return launch_project_bwd(fn, a, s);
+}
+
+// gsx_project_ewa_packed_bwd and, with `opac`, gsx_project_ewa_packed_bwd_opac: Gaussian-major through a.row_map when the caller
+// built one, else row-major into ZERO-FILLED outputs (v_opacities as well): plain stores for a single image, atomics otherwise
+static int project_packed_bwd(const char *fn, const ProjBwdArgs &a, bool opac, hipStream_t s)
+{
+    if (opac) {
+        if ((int64_t)a.B * a.N == 0) return GSX_OK; // no Gaussians: nothing to write
+        GSX_REQUIRE(a.v_opacities, "%s: null v_opacities", fn);
+        if (a.nnz <= 0) return zero_v_opacities(fn, a, s); // no rows: the cotangent is empty (its pointer may be null)
+        GSX_REQUIRE(a.v_view_opacities && a.opac_stride >= 1, "%s: null opacity cotangent", fn);
+    } else if (a.nnz <= 0) return GSX_OK;
+    int rc = check_proj_bwd(fn, a, true);
+    if (rc != GSX_OK) return rc;
+    if (a.row_map) return launch_project_bwd(fn, a, s);
+    const dim3 grid((uint32_t)ceil_div(a.nnz, 256)), block(256);
+    const bool unique = (uint64_t)a.B * a.C == 1;
+    if (a.v_viewmats) {
+        if (unique) project_packed_bwd_kernel<true, true><<<grid, block, 0, s>>>(a);
+        else project_packed_bwd_kernel<true, false><<<grid, block, 0, s>>>(a);
+    } else {
+        if (unique) project_packed_bwd_kernel<false, true><<<grid, block, 0, s>>>(a);
+        else project_packed_bwd_kernel<false, false><<<grid, block, 0, s>>>(a);
+    }
+    return check_launch(fn + 4);
 }
 
 extern "C" int gsx_project_ewa_bwd(const float *means, const float *covars, const float *quats, const float *scales,
@@ -878,21 +960,11 @@ extern "C" int gsx_project_ewa_bwd(const float *means, const float *covars, cons
                                    const float *v_compensations, float *v_means, float *v_covars, float *v_quats,
                                    float *v_scales, float *v_viewmats, void *stream)
 {
-    const int64_t count = (int64_t)B * N;
-    if (count == 0 || C == 0) return GSX_OK;
-    int rc = check_proj_common("gsx_project_ewa_bwd", means, covars, quats, scales, viewmats, Ks, camera_model);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(radii && conics && v_means2d && v_conics, "gsx_project_ewa_bwd: null input");
-    GSX_REQUIRE(v_means2d_stride >= 2 && v_conics_stride >= 3, "gsx_project_ewa_bwd: row strides must be >= 2 / >= 3");
-    ProjBwdArgs a{};
-    fill_bwd(a, means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
-             compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride, v_compensations, v_means,
-             v_covars, v_quats, v_scales, v_viewmats);
+    ProjBwdArgs a = proj_bwd_args(means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
+                                  compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride,
+                                  v_compensations, v_means, v_covars, v_quats, v_scales, v_viewmats);
     a.radii = radii;
-    const dim3 grid((uint32_t)ceil_div(count, 256)), block(256);
-    if (v_viewmats) project_bwd_kernel<true><<<grid, block, 0, (hipStream_t)stream>>>(a);
-    else project_bwd_kernel<false><<<grid, block, 0, (hipStream_t)stream>>>(a);
-    return check_launch("project_ewa_bwd");
+    return project_bwd("gsx_project_ewa_bwd", a, false, (hipStream_t)stream);
 }
 
 // gsx_project_ewa_bwd that also reduces the cotangent of the per-view opacities: v_view_opacities[(b C + c) N + g] at
@@ -909,31 +981,12 @@ extern "C" int gsx_project_ewa_bwd_opac(const float *means, const float *covars,
                                         float *v_covars, float *v_quats, float *v_scales, float *v_viewmats,
                                         float *v_opacities, void *stream)
 {
-    const int64_t count = (int64_t)B * N;
-    if (count == 0) return GSX_OK;
-    GSX_REQUIRE(v_opacities, "gsx_project_ewa_bwd_opac: null v_opacities");
-    if (C == 0) { // no views: the cotangent is empty, every Gaussian's gradient is zero
-        if (hipMemsetAsync(v_opacities, 0, (size_t)count * sizeof(float), (hipStream_t)stream) != hipSuccess) {
-            set_last_error("gsx_project_ewa_bwd_opac: memset failed");
-            return GSX_ERR_LAUNCH;
-        }
-        return GSX_OK;
-    }
-    GSX_REQUIRE(v_view_opacities && v_view_opacities_stride >= 1, "gsx_project_ewa_bwd_opac: null opacity cotangent");
-    int rc = check_proj_common("gsx_project_ewa_bwd_opac", means, covars, quats, scales, viewmats, Ks, camera_model);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(radii && conics && v_means2d && v_conics, "gsx_project_ewa_bwd_opac: null input");
-    GSX_REQUIRE(v_means2d_stride >= 2 && v_conics_stride >= 3, "gsx_project_ewa_bwd_opac: row strides must be >= 2 / >= 3");
-    ProjBwdArgs a{};
-    fill_bwd(a, means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
-             compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride, v_compensations, v_means,
-             v_covars, v_quats, v_scales, v_viewmats);
+    ProjBwdArgs a = proj_bwd_args(means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
+                                  compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride,
+                                  v_compensations, v_means, v_covars, v_quats, v_scales, v_viewmats);
     a.radii = radii;
     a.v_view_opacities = v_view_opacities; a.opac_stride = v_view_opacities_stride; a.v_opacities = v_opacities;
-    const dim3 grid((uint32_t)ceil_div(count, 256)), block(256);
-    if (v_viewmats) project_bwd_kernel<true><<<grid, block, 0, (hipStream_t)stream>>>(a);
-    else project_bwd_kernel<false><<<grid, block, 0, (hipStream_t)stream>>>(a);
-    return check_launch("project_ewa_bwd_opac");
+    return project_bwd("gsx_project_ewa_bwd_opac", a, true, (hipStream_t)stream);
 }
 
 extern "C" int gsx_project_ewa_packed_bwd(const float *means, const float *covars, const float *quats,
@@ -947,38 +1000,11 @@ extern "C" int gsx_project_ewa_packed_bwd(const float *means, const float *covar
                                           const int32_t *row_map, float *v_means, float *v_covars, float *v_quats,
                                           float *v_scales, float *v_viewmats, void *stream)
 {
-    if (nnz <= 0) return GSX_OK;
-    int rc = check_proj_common("gsx_project_ewa_packed_bwd", means, covars, quats, scales, viewmats, Ks, camera_model);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(batch_ids && camera_ids && gaussian_ids && conics && v_means2d && v_conics,
-                "gsx_project_ewa_packed_bwd: null input");
-    GSX_REQUIRE(v_means2d_stride >= 2 && v_conics_stride >= 3,
-                "gsx_project_ewa_packed_bwd: row strides must be >= 2 / >= 3");
-    ProjBwdArgs a{};
-    fill_bwd(a, means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
-             compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride, v_compensations, v_means,
-             v_covars, v_quats, v_scales, v_viewmats);
-    a.nnz = nnz; a.batch_ids = batch_ids; a.camera_ids = camera_ids; a.gaussian_ids = gaussian_ids;
-    hipStream_t s = (hipStream_t)stream;
-    if (row_map) {
-        // Gaussian-major walk through the row map: one thread per Gaussian loops over the images, every output row is
-        // written exactly once (no atomics, no zero-initialised outputs needed) — the dense kernel on packed rows
-        a.row_map = row_map;
-        const dim3 g2((uint32_t)ceil_div((int64_t)B * N, 256));
-        if (v_viewmats) project_bwd_kernel<true><<<g2, dim3(256), 0, s>>>(a);
-        else project_bwd_kernel<false><<<g2, dim3(256), 0, s>>>(a);
-        return check_launch("project_ewa_packed_bwd");
-    }
-    const dim3 grid((uint32_t)ceil_div(nnz, 256)), block(256);
-    const bool unique = (uint64_t)B * C == 1;
-    if (v_viewmats) {
-        if (unique) project_packed_bwd_kernel<true, true><<<grid, block, 0, s>>>(a);
-        else project_packed_bwd_kernel<true, false><<<grid, block, 0, s>>>(a);
-    } else {
-        if (unique) project_packed_bwd_kernel<false, true><<<grid, block, 0, s>>>(a);
-        else project_packed_bwd_kernel<false, false><<<grid, block, 0, s>>>(a);
-    }
-    return check_launch("project_ewa_packed_bwd");
+    ProjBwdArgs a = proj_bwd_args(means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
+                                  compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride,
+                                  v_compensations, v_means, v_covars, v_quats, v_scales, v_viewmats);
+    a.nnz = nnz; a.batch_ids = batch_ids; a.camera_ids = camera_ids; a.gaussian_ids = gaussian_ids; a.row_map = row_map;
+    return project_packed_bwd("gsx_project_ewa_packed_bwd", a, false, (hipStream_t)stream);
 }
 
 // gsx_project_ewa_packed_bwd (either route: with a row map Gaussian-major, without one row-major into zero-filled outputs,
@@ -997,47 +1023,12 @@ extern "C" int gsx_project_ewa_packed_bwd_opac(const float *means, const float *
                                                const int32_t *row_map, float *v_means, float *v_covars, float *v_quats,
                                                float *v_scales, float *v_viewmats, float *v_opacities, void *stream)
 {
-    hipStream_t s = (hipStream_t)stream;
-    if ((int64_t)B * N == 0) return GSX_OK; // no Gaussians: nothing to write
-    GSX_REQUIRE(v_opacities, "gsx_project_ewa_packed_bwd_opac: null v_opacities");
-    if (nnz <= 0) { // no rows: the cotangent is empty (its pointer may be null), every Gaussian's gradient is zero
-        if (hipMemsetAsync(v_opacities, 0, (size_t)B * N * sizeof(float), s) != hipSuccess) {
-            set_last_error("gsx_project_ewa_packed_bwd_opac: memset failed");
-            return GSX_ERR_LAUNCH;
-        }
-        return GSX_OK;
-    }
-    GSX_REQUIRE(v_view_opacities && v_view_opacities_stride >= 1, "gsx_project_ewa_packed_bwd_opac: null opacity cotangent");
-    int rc = check_proj_common("gsx_project_ewa_packed_bwd_opac", means, covars, quats, scales, viewmats, Ks, camera_model);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(batch_ids && camera_ids && gaussian_ids && conics && v_means2d && v_conics,
-                "gsx_project_ewa_packed_bwd_opac: null input");
-    GSX_REQUIRE(v_means2d_stride >= 2 && v_conics_stride >= 3,
-                "gsx_project_ewa_packed_bwd_opac: row strides must be >= 2 / >= 3");
-    ProjBwdArgs a{};
-    fill_bwd(a, means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
-             compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride, v_compensations, v_means,
-             v_covars, v_quats, v_scales, v_viewmats);
-    a.nnz = nnz; a.batch_ids = batch_ids; a.camera_ids = camera_ids; a.gaussian_ids = gaussian_ids;
-    a.row_map = row_map;
+    ProjBwdArgs a = proj_bwd_args(means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
+                                  compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride,
+                                  v_compensations, v_means, v_covars, v_quats, v_scales, v_viewmats);
+    a.nnz = nnz; a.batch_ids = batch_ids; a.camera_ids = camera_ids; a.gaussian_ids = gaussian_ids; a.row_map = row_map;
     a.v_view_opacities = v_view_opacities; a.opac_stride = v_view_opacities_stride; a.v_opacities = v_opacities;
-    if (row_map) { // Gaussian-major: every output row written once
-        const dim3 g2((uint32_t)ceil_div((int64_t)B * N, 256));
-        if (v_viewmats) project_bwd_kernel<true><<<g2, dim3(256), 0, s>>>(a);
-        else project_bwd_kernel<false><<<g2, dim3(256), 0, s>>>(a);
-        return check_launch("project_ewa_packed_bwd_opac");
-    }
-    // row-major: into ZERO-FILLED outputs (v_opacities as well), plain stores for a single image, atomics otherwise
-    const dim3 grid((uint32_t)ceil_div(nnz, 256)), block(256);
-    const bool unique = (uint64_t)B * C == 1;
-    if (v_viewmats) {
-        if (unique) project_packed_bwd_kernel<true, true><<<grid, block, 0, s>>>(a);
-        else project_packed_bwd_kernel<true, false><<<grid, block, 0, s>>>(a);
-    } else {
-        if (unique) project_packed_bwd_kernel<false, true><<<grid, block, 0, s>>>(a);
-        else project_packed_bwd_kernel<false, false><<<grid, block, 0, s>>>(a);
-    }
-    return check_launch("project_ewa_packed_bwd_opac");
+    return project_packed_bwd("gsx_project_ewa_packed_bwd_opac", a, true, (hipStream_t)stream);
 }
 
 // sparse_grad=True (reference Projection.cpp:1125-1200, kernel ProjectionEWA3DGSPacked.cu:385-684): the per-Gaussian
@@ -1055,18 +1046,13 @@ extern "C" int gsx_project_ewa_packed_bwd_rows(const float *means, const float *
                                                float *v_scales_rows, float *v_viewmats, void *stream)
 {
     if (nnz <= 0) return GSX_OK;
-    int rc = check_proj_common("gsx_project_ewa_packed_bwd_rows", means, covars, quats, scales, viewmats, Ks, camera_model);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(batch_ids && camera_ids && gaussian_ids && conics && v_means2d && v_conics,
-                "gsx_project_ewa_packed_bwd_rows: null input");
-    GSX_REQUIRE(v_means2d_stride >= 2 && v_conics_stride >= 3,
-                "gsx_project_ewa_packed_bwd_rows: row strides must be >= 2 / >= 3");
-    ProjBwdArgs a{};
-    fill_bwd(a, means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
-             compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride, v_compensations,
-             v_means_rows, v_covars_rows, v_quats_rows, v_scales_rows, v_viewmats);
+    ProjBwdArgs a = proj_bwd_args(means, covars, quats, scales, viewmats, Ks, B, C, N, width, height, eps2d, camera_model, conics,
+                                  compensations, v_means2d, v_means2d_stride, v_depths, v_conics, v_conics_stride,
+                                  v_compensations, v_means_rows, v_covars_rows, v_quats_rows, v_scales_rows, v_viewmats);
     a.nnz = nnz; a.batch_ids = batch_ids; a.camera_ids = camera_ids; a.gaussian_ids = gaussian_ids;
     a.rows_out = 1;
+    int rc = check_proj_bwd("gsx_project_ewa_packed_bwd_rows", a, true);
+    if (rc != GSX_OK) return rc;
     const dim3 grid((uint32_t)ceil_div(nnz, 256)), block(256);
     if (v_viewmats) project_packed_bwd_kernel<true, true><<<grid, block, 0, (hipStream_t)stream>>>(a);
     else project_packed_bwd_kernel<false, true><<<grid, block, 0, (hipStream_t)stream>>>(a);

@@ -468,6 +468,59 @@ extern "C" int gsx_project_2dgs_packed_write(const float *means, const float *qu
     return check_launch("project_2dgs_packed_write");
 }
 
+// ---- backward, host side: the entries fill the kernel's argument block and forward to one body per kernel; `fn` is the entry's
+// own name for the messages (the launch names drop its gsx_ prefix: fn + 4) ----
+
+// v_row_stride = 0: v_means2d / v_ray_transforms / v_normals are contiguous arrays; else columns of rows that wide.
+// v_depths_stride likewise (0 = contiguous)
+static Proj2BwdArgs proj2_bwd_args(const float *means, const float *quats, const float *scales, const float *viewmats,
+                                   const float *Ks, uint32_t B, uint32_t C, uint32_t N, const float *ray_transforms,
+                                   const float *v_means2d, const float *v_depths, const float *v_ray_transforms,
+                                   const float *v_normals, uint32_t v_row_stride, uint32_t v_depths_stride, float *v_means,
+                                   float *v_quats, float *v_scales, float *v_viewmats)
+{
+    Proj2BwdArgs a{};
+    a.means = means; a.quats = quats; a.scales = scales; a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N;
+    a.ray_transforms = ray_transforms; a.v_means2d = v_means2d; a.v_depths = v_depths;
+    a.v_ray_transforms = v_ray_transforms; a.v_normals = v_normals;
+    a.m2_stride = v_row_stride ? v_row_stride : 2u; a.rt_stride = v_row_stride ? v_row_stride : 9u;
+    a.n_stride = v_row_stride ? v_row_stride : 3u;
+    a.depth_stride = v_depths_stride ? v_depths_stride : 1u;
+    a.v_means = v_means; a.v_quats = v_quats; a.v_scales = v_scales; a.v_viewmats = v_viewmats;
+    return a;
+}
+
+// gsx_project_2dgs_bwd and, with `opac`, gsx_project_2dgs_bwd_opac
+static int project2_bwd(const char *fn, const Proj2BwdArgs &a, bool opac, hipStream_t s)
+{
+    if ((int64_t)a.B * a.N == 0) return GSX_OK;
+    GSX_REQUIRE(!opac || a.v_opacities, "%s: null v_opacities", fn);
+    int rc = check2(fn, a.means, a.quats, a.scales, a.viewmats, a.Ks);
+    if (rc != GSX_OK) return rc;
+    GSX_REQUIRE(a.C == 0 || (a.radii && a.ray_transforms && a.v_means2d && a.v_ray_transforms && a.v_normals
+                             && (!opac || (a.v_view_opacities && a.opac_stride >= 1))), "%s: null input", fn);
+    GSX_REQUIRE(a.v_means && a.v_quats && a.v_scales, "%s: null output", fn);
+    const dim3 grid((uint32_t)ceil_div((int64_t)a.B * a.N, 256));
+    if (a.v_viewmats) project2_bwd_kernel<true><<<grid, dim3(256), 0, s>>>(a);
+    else project2_bwd_kernel<false><<<grid, dim3(256), 0, s>>>(a);
+    return check_launch(fn + 4);
+}
+
+// gsx_project_2dgs_packed_bwd and (a.rows_out) gsx_project_2dgs_packed_bwd_rows
+static int project2_packed_bwd(const char *fn, const Proj2BwdArgs &a, hipStream_t s)
+{
+    if (a.nnz == 0) return GSX_OK;
+    int rc = check2(fn, a.means, a.quats, a.scales, a.viewmats, a.Ks);
+    if (rc != GSX_OK) return rc;
+    GSX_REQUIRE(a.batch_ids && a.camera_ids && a.gaussian_ids && a.ray_transforms && a.v_means2d && a.v_ray_transforms
+                && a.v_normals, "%s: null input", fn);
+    GSX_REQUIRE(a.v_means && a.v_quats && a.v_scales, "%s: null output", fn);
+    const dim3 grid((uint32_t)ceil_div(a.nnz, 256));
+    if (a.v_viewmats) project2_packed_bwd_kernel<true><<<grid, dim3(256), 0, s>>>(a);
+    else project2_packed_bwd_kernel<false><<<grid, dim3(256), 0, s>>>(a);
+    return check_launch(fn + 4);
+}
+
 extern "C" int gsx_project_2dgs_bwd(const float *means, const float *quats, const float *scales, const float *viewmats,
                                     const float *Ks, uint32_t B, uint32_t C, uint32_t N, const int32_t *radii,
                                     const float *ray_transforms, const float *v_means2d, const float *v_depths,
@@ -475,24 +528,11 @@ extern "C" int gsx_project_2dgs_bwd(const float *means, const float *quats, cons
                                     uint32_t v_depths_stride, float *v_means, float *v_quats,
                                     float *v_scales, float *v_viewmats, void *stream)
 {
-    if ((int64_t)B * N == 0) return GSX_OK;
-    int rc = check2("gsx_project_2dgs_bwd", means, quats, scales, viewmats, Ks);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(C == 0 || (radii && ray_transforms && v_means2d && v_ray_transforms && v_normals),
-                "gsx_project_2dgs_bwd: null input");
-    GSX_REQUIRE(v_means && v_quats && v_scales, "gsx_project_2dgs_bwd: null output");
-    Proj2BwdArgs a{};
-    a.means = means; a.quats = quats; a.scales = scales; a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N;
-    a.radii = radii; a.ray_transforms = ray_transforms; a.v_means2d = v_means2d; a.v_depths = v_depths;
-    a.v_ray_transforms = v_ray_transforms; a.v_normals = v_normals;
-    a.m2_stride = v_row_stride ? v_row_stride : 2u; a.rt_stride = v_row_stride ? v_row_stride : 9u;
-    a.n_stride = v_row_stride ? v_row_stride : 3u;
-    a.depth_stride = v_depths_stride ? v_depths_stride : 1u;
-    a.v_means = v_means; a.v_quats = v_quats; a.v_scales = v_scales; a.v_viewmats = v_viewmats;
-    const dim3 grid((uint32_t)ceil_div((int64_t)B * N, 256));
-    if (v_viewmats) project2_bwd_kernel<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(a);
-    else project2_bwd_kernel<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(a);
-    return check_launch("project_2dgs_bwd");
+    Proj2BwdArgs a = proj2_bwd_args(means, quats, scales, viewmats, Ks, B, C, N, ray_transforms, v_means2d, v_depths,
+                                    v_ray_transforms, v_normals, v_row_stride, v_depths_stride, v_means, v_quats, v_scales,
+                                    v_viewmats);
+    a.radii = radii;
+    return project2_bwd("gsx_project_2dgs_bwd", a, false, (hipStream_t)stream);
 }
 
 // gsx_project_2dgs_bwd that also reduces the cotangent of the per-view opacities (see gsx_project_ewa_bwd_opac):
@@ -505,26 +545,12 @@ extern "C" int gsx_project_2dgs_bwd_opac(const float *means, const float *quats,
                                          uint32_t v_view_opacities_stride, float *v_means,
                                          float *v_quats, float *v_scales, float *v_viewmats, float *v_opacities, void *stream)
 {
-    if ((int64_t)B * N == 0) return GSX_OK;
-    GSX_REQUIRE(v_opacities, "gsx_project_2dgs_bwd_opac: null v_opacities");
-    int rc = check2("gsx_project_2dgs_bwd_opac", means, quats, scales, viewmats, Ks);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(C == 0 || (radii && ray_transforms && v_means2d && v_ray_transforms && v_normals && v_view_opacities
-                           && v_view_opacities_stride >= 1), "gsx_project_2dgs_bwd_opac: null input");
-    GSX_REQUIRE(v_means && v_quats && v_scales, "gsx_project_2dgs_bwd_opac: null output");
-    Proj2BwdArgs a{};
-    a.means = means; a.quats = quats; a.scales = scales; a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N;
-    a.radii = radii; a.ray_transforms = ray_transforms; a.v_means2d = v_means2d; a.v_depths = v_depths;
-    a.v_ray_transforms = v_ray_transforms; a.v_normals = v_normals;
-    a.m2_stride = v_row_stride ? v_row_stride : 2u; a.rt_stride = v_row_stride ? v_row_stride : 9u;
-    a.n_stride = v_row_stride ? v_row_stride : 3u;
-    a.depth_stride = v_depths_stride ? v_depths_stride : 1u;
-    a.v_means = v_means; a.v_quats = v_quats; a.v_scales = v_scales; a.v_viewmats = v_viewmats;
+    Proj2BwdArgs a = proj2_bwd_args(means, quats, scales, viewmats, Ks, B, C, N, ray_transforms, v_means2d, v_depths,
+                                    v_ray_transforms, v_normals, v_row_stride, v_depths_stride, v_means, v_quats, v_scales,
+                                    v_viewmats);
+    a.radii = radii;
     a.v_view_opacities = v_view_opacities; a.opac_stride = v_view_opacities_stride; a.v_opacities = v_opacities;
-    const dim3 grid((uint32_t)ceil_div((int64_t)B * N, 256));
-    if (v_viewmats) project2_bwd_kernel<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(a);
-    else project2_bwd_kernel<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(a);
-    return check_launch("project_2dgs_bwd_opac");
+    return project2_bwd("gsx_project_2dgs_bwd_opac", a, true, (hipStream_t)stream);
 }
 
 extern "C" int gsx_project_2dgs_packed_bwd(const float *means, const float *quats, const float *scales,
@@ -536,25 +562,10 @@ extern "C" int gsx_project_2dgs_packed_bwd(const float *means, const float *quat
                                            float *v_quats, float *v_scales,
                                            float *v_viewmats, void *stream)
 {
-    if (nnz == 0) return GSX_OK;
-    int rc = check2("gsx_project_2dgs_packed_bwd", means, quats, scales, viewmats, Ks);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(batch_ids && camera_ids && gaussian_ids && ray_transforms && v_means2d && v_ray_transforms
-                && v_normals, "gsx_project_2dgs_packed_bwd: null input");
-    GSX_REQUIRE(v_means && v_quats && v_scales, "gsx_project_2dgs_packed_bwd: null output");
-    Proj2BwdArgs a{};
-    a.means = means; a.quats = quats; a.scales = scales; a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N;
+    Proj2BwdArgs a = proj2_bwd_args(means, quats, scales, viewmats, Ks, B, C, N, ray_transforms, v_means2d, v_depths,
+                                    v_ray_transforms, v_normals, v_row_stride, 0, v_means, v_quats, v_scales, v_viewmats);
     a.nnz = nnz; a.batch_ids = batch_ids; a.camera_ids = camera_ids; a.gaussian_ids = gaussian_ids;
-    a.ray_transforms = ray_transforms; a.v_means2d = v_means2d; a.v_depths = v_depths;
-    a.v_ray_transforms = v_ray_transforms; a.v_normals = v_normals;
-    a.m2_stride = v_row_stride ? v_row_stride : 2u; a.rt_stride = v_row_stride ? v_row_stride : 9u;
-    a.n_stride = v_row_stride ? v_row_stride : 3u;
-    a.depth_stride = 1u;
-    a.v_means = v_means; a.v_quats = v_quats; a.v_scales = v_scales; a.v_viewmats = v_viewmats;
-    const dim3 grid((uint32_t)ceil_div(nnz, 256));
-    if (v_viewmats) project2_packed_bwd_kernel<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(a);
-    else project2_packed_bwd_kernel<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(a);
-    return check_launch("project_2dgs_packed_bwd");
+    return project2_packed_bwd("gsx_project_2dgs_packed_bwd", a, (hipStream_t)stream);
 }
 
 // sparse_grad=True (reference Projection.cpp:1780-1863): v_means / v_quats / v_scales are [nnz, .] rows, one per packed row,
@@ -568,24 +579,9 @@ extern "C" int gsx_project_2dgs_packed_bwd_rows(const float *means, const float 
                                            float *v_quats, float *v_scales,
                                            float *v_viewmats, void *stream)
 {
-    if (nnz == 0) return GSX_OK;
-    int rc = check2("gsx_project_2dgs_packed_bwd_rows", means, quats, scales, viewmats, Ks);
-    if (rc != GSX_OK) return rc;
-    GSX_REQUIRE(batch_ids && camera_ids && gaussian_ids && ray_transforms && v_means2d && v_ray_transforms
-                && v_normals, "gsx_project_2dgs_packed_bwd_rows: null input");
-    GSX_REQUIRE(v_means && v_quats && v_scales, "gsx_project_2dgs_packed_bwd_rows: null output");
-    Proj2BwdArgs a{};
-    a.means = means; a.quats = quats; a.scales = scales; a.viewmats = viewmats; a.Ks = Ks; a.B = B; a.C = C; a.N = N;
+    Proj2BwdArgs a = proj2_bwd_args(means, quats, scales, viewmats, Ks, B, C, N, ray_transforms, v_means2d, v_depths,
+                                    v_ray_transforms, v_normals, v_row_stride, 0, v_means, v_quats, v_scales, v_viewmats);
     a.nnz = nnz; a.batch_ids = batch_ids; a.camera_ids = camera_ids; a.gaussian_ids = gaussian_ids;
-    a.ray_transforms = ray_transforms; a.v_means2d = v_means2d; a.v_depths = v_depths;
-    a.v_ray_transforms = v_ray_transforms; a.v_normals = v_normals;
-    a.m2_stride = v_row_stride ? v_row_stride : 2u; a.rt_stride = v_row_stride ? v_row_stride : 9u;
-    a.n_stride = v_row_stride ? v_row_stride : 3u;
-    a.depth_stride = 1u;
-    a.v_means = v_means; a.v_quats = v_quats; a.v_scales = v_scales; a.v_viewmats = v_viewmats;
     a.rows_out = 1;
-    const dim3 grid((uint32_t)ceil_div(nnz, 256));
-    if (v_viewmats) project2_packed_bwd_kernel<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(a);
-    else project2_packed_bwd_kernel<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(a);
-    return check_launch("project_2dgs_packed_bwd_rows");
+    return project2_packed_bwd("gsx_project_2dgs_packed_bwd_rows", a, (hipStream_t)stream);
 }

@@ -845,14 +845,7 @@ static int launch2_bwd(const Raster2DArgs &a, hipStream_t stream)
 template <bool ABS>
 static int dispatch2_bwd(const Raster2DArgs &a, hipStream_t s)
 {
-    const uint32_t n = a.cdim;
-    if (n <= 1) return launch2_bwd<1, ABS>(a, s);
-    if (n <= 2) return launch2_bwd<2, ABS>(a, s);
-    if (n <= 3) return launch2_bwd<3, ABS>(a, s);
-    if (n <= 4) return launch2_bwd<4, ABS>(a, s);
-    if (n <= 8) return launch2_bwd<8, ABS>(a, s);
-    if (n <= 16) return launch2_bwd<16, ABS>(a, s);
-    return launch2_bwd<32, ABS>(a, s);
+    return with_channels(a.cdim, [&](auto ch) { return launch2_bwd<ch(), ABS>(a, s); });
 }
 
 } // namespace gsx
@@ -883,13 +876,7 @@ extern "C" int gsx_raster2d_fwd(const float *means2d, const float *ray_transform
     a.render_colors = render_colors; a.render_alphas = render_alphas; a.render_normals = render_normals;
     a.render_distort = render_distort; a.render_median = render_median; a.last_ids = last_ids; a.median_ids = median_ids;
     hipStream_t s = (hipStream_t)stream;
-    if (cdim <= 1) return launch2_fwd<1>(a, s);
-    if (cdim <= 2) return launch2_fwd<2>(a, s);
-    if (cdim <= 3) return launch2_fwd<3>(a, s);
-    if (cdim <= 4) return launch2_fwd<4>(a, s);
-    if (cdim <= 8) return launch2_fwd<8>(a, s);
-    if (cdim <= 16) return launch2_fwd<16>(a, s);
-    return launch2_fwd<32>(a, s);
+    return with_channels(cdim, [&](auto ch) { return launch2_fwd<ch()>(a, s); });
 }
 
 extern "C" int gsx_raster2d_bwd(const float *means2d, const float *ray_transforms, const float *colors,
@@ -943,16 +930,9 @@ extern "C" int gsx_raster2d_bwd_fill(const float *means2d, const float *ray_tran
 {
     GSX_REQUIRE(tile_size >= 1 && tile_size <= 16, "gsx_raster2d_bwd: tile_size must be in [1,16], got %u", tile_size);
     GSX_REQUIRE(cdim >= 1 && cdim <= 32, "gsx_raster2d_bwd: unsupported number of channels %u (1..32)", cdim);
-    int64_t fill_bytes = v_rows_to_fill > 0 ? v_rows_to_fill * (int64_t)row_stride * 4 : 0;
-    auto fill_now      = [&]() -> int { // rows not filled by a kernel of this call
-        if (fill_bytes > 0 && v_rows && hipMemsetAsync(v_rows, 0, (size_t)fill_bytes, (hipStream_t)stream) != hipSuccess) {
-            set_last_error("gsx_raster2d_bwd_fill: memset failed");
-            return GSX_ERR_LAUNCH;
-        }
-        fill_bytes = 0;
-        return GSX_OK;
-    };
-    if (n_isects == 0) return fill_now(); // no intersections: nothing to add to the (zero-filled, possibly empty) gradient rows
+    RowFill fill{"gsx_raster2d_bwd_fill", v_rows, v_rows_to_fill > 0 ? v_rows_to_fill * (int64_t)row_stride * 4 : 0,
+                 (hipStream_t)stream};
+    if (n_isects == 0) return fill.now(); // no intersections: nothing to add to the (zero-filled, possibly empty) gradient rows
     GSX_REQUIRE(v_rows, "gsx_raster2d_bwd: null gradient output");
     GSX_REQUIRE(row_stride >= 17u + (has_abs ? 2u : 0u) + cdim, "gsx_raster2d_bwd: row_stride %u too small", row_stride);
     GSX_REQUIRE(n_isects == 0 || (means2d && ray_transforms && colors && opacities && normals && flatten_ids
@@ -971,14 +951,8 @@ extern "C" int gsx_raster2d_bwd_fill(const float *means2d, const float *ray_tran
     a.v_render_distort = v_render_distort; a.v_render_median = v_render_median;
     a.v_rows = v_rows; a.row_stride = row_stride;
     hipStream_t s = (hipStream_t)stream;
-    {
-        int rc               = GSX_OK;
-        const bool in_kernel = fill_bytes > 0 && (reinterpret_cast<uintptr_t>(v_rows) & 15u) == 0;
-        a.tile_order = build_tile_order(isect_offsets, last_ids, n_images, tile_size, tile_w, tile_h, width, height, n_isects,
-                                        workspace, workspace_bytes, s, &rc, in_kernel ? v_rows : nullptr, fill_bytes);
-        if (rc != GSX_OK) return rc;
-        if (a.tile_order && in_kernel) fill_bytes = 0; // done by the cost kernel
-    }
-    if (int rc = fill_now(); rc != GSX_OK) return rc;
+    int rc       = GSX_OK; // the order is built whatever the variant (unlike gsx_raster3d_bwd_fill)
+    a.tile_order = fill.tile_order(a, workspace, workspace_bytes, &rc);
+    if (rc != GSX_OK || (rc = fill.now()) != GSX_OK) return rc;
     return has_abs ? dispatch2_bwd<true>(a, s) : dispatch2_bwd<false>(a, s);
 }

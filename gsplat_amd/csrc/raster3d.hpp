@@ -15,6 +15,8 @@
 #pragma once
 #include "common.hpp"
 
+#include <type_traits>
+
 namespace gsx {
 
 struct Raster3DArgs {
@@ -79,6 +81,60 @@ struct Raster3DArgs {
     // backward, dense layouts: workgroup -> tile map sorted by work (raster3d_bwd.hip: tile_order_*), or null = launch order
     const int32_t *tile_order;
 };
+
+// ---- host side: the argument block of a compositing call. One builder for what every call sets, so that an entry point states
+// only what is its own ----
+// geometry, channel count, the forward's inputs and its per-pixel results (outputs of a forward call, inputs of a backward one)
+inline Raster3DArgs raster3d_args(uint32_t n_images, uint32_t n_isects, uint32_t cdim, uint32_t width, uint32_t height,
+                                  uint32_t tile_size, uint32_t tile_w, uint32_t tile_h, const float *means2d, const float *conics,
+                                  const float *colors, const float *opacities, const float *backgrounds, const uint8_t *masks,
+                                  const int32_t *isect_offsets, const int32_t *flatten_ids, float *render_colors,
+                                  const float *render_alphas, const int32_t *last_ids)
+{
+    Raster3DArgs a{};
+    a.n_images = n_images; a.n_isects = n_isects; a.width = width; a.height = height;
+    a.tile_size = tile_size; a.tile_w = tile_w; a.tile_h = tile_h; a.cdim = cdim;
+    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
+    a.backgrounds = backgrounds; a.masks = masks; a.isect_offsets = isect_offsets; a.flatten_ids = flatten_ids;
+    a.render_colors = render_colors; a.render_alphas = const_cast<float *>(render_alphas);
+    a.last_ids = const_cast<int32_t *>(last_ids);
+    return a;
+}
+// + the cotangents and the gradient rows of a backward call
+inline void raster3d_set_bwd(Raster3DArgs &a, const float *v_render_colors, const float *v_render_alphas, float *v_rows,
+                             uint32_t row_stride)
+{
+    a.v_render_colors = v_render_colors; a.v_render_alphas = v_render_alphas;
+    a.v_rows = v_rows; a.row_stride = row_stride;
+}
+// + the sparse pixel layout (a.isect_offsets then holds the per-ACTIVE-tile offsets)
+inline void raster3d_set_sparse(Raster3DArgs &a, const int32_t *active_tiles, const uint64_t *tile_pixel_mask,
+                                const int64_t *tile_pixel_cumsum, const int64_t *pixel_map, uint32_t n_active,
+                                uint32_t words_per_tile)
+{
+    a.sp_active_tiles = active_tiles; a.sp_pixel_mask = tile_pixel_mask; a.sp_pixel_cumsum = tile_pixel_cumsum;
+    a.sp_pixel_map = pixel_map; a.n_active = n_active; a.sp_words = words_per_tile;
+}
+
+// Run-time channel count -> the kernel instantiation that holds it: calls f(std::integral_constant<int, CH>) with the smallest
+// CH >= n of 1, 2, 3, 4 (with_channels4) or of 1, 2, 3, 4, 8, 16, 32 (with_channels) and returns what f returns. Inside f,
+// ch() is a constant expression: launch<ch()>(...).
+template <class F>
+inline auto with_channels4(uint32_t n, F &&f)
+{
+    if (n <= 1) return f(std::integral_constant<int, 1>{});
+    if (n <= 2) return f(std::integral_constant<int, 2>{});
+    if (n <= 3) return f(std::integral_constant<int, 3>{});
+    return f(std::integral_constant<int, 4>{});
+}
+template <class F>
+inline auto with_channels(uint32_t n, F &&f)
+{
+    if (n <= 4) return with_channels4(n, f);
+    if (n <= 8) return f(std::integral_constant<int, 8>{});
+    if (n <= 16) return f(std::integral_constant<int, 16>{});
+    return f(std::integral_constant<int, 32>{});
+}
 
 // Block index -> (image, tile) with an XCD-aware remap: hardware places workgroup b on
 // XCD b % 8 (MI355X_MICROARCH.md "Workgroup dispatch"); neighbouring tiles share Gaussians,
@@ -195,6 +251,36 @@ int64_t tile_order_workspace_bytes(uint32_t n_images, uint32_t tile_w, uint32_t 
 const int32_t *build_tile_order(const int32_t *isect_offsets, const int32_t *last_ids, uint32_t n_images, uint32_t tile_size,
                                 uint32_t tile_w, uint32_t tile_h, uint32_t width, uint32_t height, uint32_t n_isects, void *ws,
                                 int64_t ws_bytes, hipStream_t stream, int *rc, void *zero_ptr = nullptr, int64_t zero_bytes = 0);
+
+// The gradient rows that a compositing backward call fills with zeros itself (gsx_raster3d_bwd_fill, gsx_raster2d_bwd_fill:
+// v_rows_to_fill > 0): inside the tile-order cost kernel when one is launched, with a memset otherwise. `fn` names the entry
+// in the message.
+struct RowFill {
+    const char *fn;
+    float *rows;
+    int64_t bytes;
+    hipStream_t stream;
+    // build_tile_order() that zeroes the rows on its way where it can (16-byte aligned rows, an order is built)
+    template <class Args> // Raster3DArgs or Raster2DArgs
+    const int32_t *tile_order(const Args &a, void *ws, int64_t ws_bytes, int *rc)
+    {
+        const bool in_kernel = bytes > 0 && (reinterpret_cast<uintptr_t>(rows) & 15u) == 0;
+        const int32_t *order = build_tile_order(a.isect_offsets, a.last_ids, a.n_images, a.tile_size, a.tile_w, a.tile_h, a.width,
+                                                a.height, a.n_isects, ws, ws_bytes, stream, rc, in_kernel ? rows : nullptr, bytes);
+        if (*rc == GSX_OK && order && in_kernel) bytes = 0; // done by the cost kernel
+        return order;
+    }
+    // the rows not filled by a kernel of this call
+    int now()
+    {
+        if (bytes > 0 && rows && hipMemsetAsync(rows, 0, (size_t)bytes, stream) != hipSuccess) {
+            set_last_error("%s: memset failed", fn);
+            return GSX_ERR_LAUNCH;
+        }
+        bytes = 0;
+        return GSX_OK;
+    }
+};
 
 // Wide colour rows (5 .. 32 channels per launch, 16 x 16 tiles, no segments) on the matrix cores: raster3d_fwd_m.hip.
 bool raster3d_fwd_m_applies(const Raster3DArgs &a);

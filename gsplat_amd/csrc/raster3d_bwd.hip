@@ -1152,10 +1152,9 @@ int raster3d_bwd_t_launch_items(const Raster3DArgs &a, hipStream_t stream)
 {
     const uint32_t grid = ((a.seg_grid + 7u) / 8u) * 8u;
     if (grid == 0) return GSX_OK;
-    if (a.nch <= 1) raster3d_bwd_t_kernel<1><<<dim3(grid), dim3(256), BwdTCfg<1>::smem, stream>>>(a);
-    else if (a.nch <= 2) raster3d_bwd_t_kernel<2><<<dim3(grid), dim3(256), BwdTCfg<2>::smem, stream>>>(a);
-    else if (a.nch <= 3) raster3d_bwd_t_kernel<3><<<dim3(grid), dim3(256), BwdTCfg<3>::smem, stream>>>(a);
-    else raster3d_bwd_t_kernel<4><<<dim3(grid), dim3(256), BwdTCfg<4>::smem, stream>>>(a);
+    with_channels4(a.nch, [&](auto ch) {
+        raster3d_bwd_t_kernel<ch()><<<dim3(grid), dim3(256), BwdTCfg<ch()>::smem, stream>>>(a);
+    });
     return check_launch("raster3d_bwd_t(segments)");
 }
 bool raster3d_bwd_uses_variant_t() { return use_variant_t(); }
@@ -1172,13 +1171,7 @@ static int bwd_dispatch(Raster3DArgs a, hipStream_t stream)
         a.first_chunk      = first ? 1u : 0u;
         int rc;
         if (bwd_variant() != 'r' && raster3d_bwd_m_applies(a, ABS)) rc = raster3d_bwd_m_launch(a, stream); // 5 .. 32 channels: raster3d_bwd_m.hip
-        else if (n <= 1) rc = launch_bwd<1, ABS>(a, stream);
-        else if (n <= 2) rc = launch_bwd<2, ABS>(a, stream);
-        else if (n <= 3) rc = launch_bwd<3, ABS>(a, stream);
-        else if (n <= 4) rc = launch_bwd<4, ABS>(a, stream);
-        else if (n <= 8) rc = launch_bwd<8, ABS>(a, stream);
-        else if (n <= 16) rc = launch_bwd<16, ABS>(a, stream);
-        else rc = launch_bwd<32, ABS>(a, stream);
+        else rc = with_channels(n, [&](auto ch) { return launch_bwd<ch(), ABS>(a, stream); });
         if (rc != GSX_OK) return rc;
         off += n;
         first = false;
@@ -1236,32 +1229,20 @@ extern "C" int gsx_raster3d_bwd_fill(
     int64_t v_colors_pixel_stride, int64_t v_colors_channel_stride, void *workspace, int64_t workspace_bytes, void *stream)
 {
     using namespace gsx;
-    int64_t fill_bytes = v_rows_to_fill > 0 ? v_rows_to_fill * (int64_t)row_stride * 4 : 0;
-    auto fill_now      = [&]() -> int { // rows not filled by a kernel of this call
-        if (fill_bytes > 0 && v_rows && hipMemsetAsync(v_rows, 0, (size_t)fill_bytes, (hipStream_t)stream) != hipSuccess) {
-            set_last_error("gsx_raster3d_bwd_fill: memset failed");
-            return GSX_ERR_LAUNCH;
-        }
-        fill_bytes = 0;
-        return GSX_OK;
-    };
+    RowFill fill{"gsx_raster3d_bwd_fill", v_rows, v_rows_to_fill > 0 ? v_rows_to_fill * (int64_t)row_stride * 4 : 0,
+                 (hipStream_t)stream};
     GSX_REQUIRE(tile_size >= 1 && tile_size <= 16, "gsx_raster3d_bwd: tile_size must be in [1,16], got %u", tile_size);
     GSX_REQUIRE(cdim >= 1, "gsx_raster3d_bwd: channels must be >= 1");
-    if (n_isects == 0) return fill_now(); // no intersections: nothing to add to the (zero-filled, possibly empty) gradient rows
+    if (n_isects == 0) return fill.now(); // no intersections: nothing to add to the (zero-filled, possibly empty) gradient rows
     GSX_REQUIRE(v_rows, "gsx_raster3d_bwd: null gradient output");
     GSX_REQUIRE(row_stride >= 6u + (has_abs ? 2u : 0u) + cdim,
                 "gsx_raster3d_bwd: row_stride %u too small for 6%s + %u channels", row_stride, has_abs ? " + 2" : "", cdim);
     GSX_REQUIRE(n_isects == 0 || (means2d && conics && colors && opacities && flatten_ids && render_alphas && last_ids
                                   && v_render_colors && isect_offsets),
                 "gsx_raster3d_bwd: null input");
-    Raster3DArgs a{};
-    a.n_images = n_images; a.n_isects = n_isects; a.width = width; a.height = height;
-    a.tile_size = tile_size; a.tile_w = tile_w; a.tile_h = tile_h; a.cdim = cdim;
-    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
-    a.backgrounds = backgrounds; a.masks = masks; a.isect_offsets = isect_offsets; a.flatten_ids = flatten_ids;
-    a.render_alphas = const_cast<float *>(render_alphas); a.last_ids = const_cast<int32_t *>(last_ids);
-    a.v_render_colors = v_render_colors; a.v_render_alphas = v_render_alphas;
-    a.v_rows = v_rows; a.row_stride = row_stride;
+    Raster3DArgs a = raster3d_args(n_images, n_isects, cdim, width, height, tile_size, tile_w, tile_h, means2d, conics, colors,
+                                   opacities, backgrounds, masks, isect_offsets, flatten_ids, nullptr, render_alphas, last_ids);
+    raster3d_set_bwd(a, v_render_colors, v_render_alphas, v_rows, row_stride);
     if (v_colors_pixel_stride >= 0) { // cotangents read in place from a layout that is linear in the pixel index
         GSX_REQUIRE(v_colors_channel_stride >= 0, "gsx_raster3d_bwd_ws: negative channel stride");
         a.vrc_strided = 1u; a.vrc_ps = v_colors_pixel_stride; a.vrc_cs = v_colors_channel_stride;
@@ -1271,15 +1252,10 @@ extern "C" int gsx_raster3d_bwd_fill(
     const bool wide_m = cdim > 4 && bwd_variant() != 'r' && raster3d_bwd_m_applies(a, has_abs != 0);
     if (wide_m || (bwd_variant() == 'w' ? (tile_size == 16 && cdim <= 4) : (!has_abs && cdim <= 4 && bwd_variant() != 'r'))) {
         int rc       = GSX_OK;
-        const bool in_kernel = fill_bytes > 0 && (reinterpret_cast<uintptr_t>(v_rows) & 15u) == 0;
-        a.tile_order = a.sp_active_tiles ? nullptr
-                                         : build_tile_order(a.isect_offsets, a.last_ids, a.n_images, a.tile_size, a.tile_w, a.tile_h,
-                                                            a.width, a.height, a.n_isects, workspace, workspace_bytes,
-                                                            (hipStream_t)stream, &rc, in_kernel ? v_rows : nullptr, fill_bytes);
+        a.tile_order = fill.tile_order(a, workspace, workspace_bytes, &rc);
         if (rc != GSX_OK) return rc;
-        if (a.tile_order && in_kernel) fill_bytes = 0; // done by the cost kernel
     }
-    if (int rc = fill_now(); rc != GSX_OK) return rc;
+    if (int rc = fill.now(); rc != GSX_OK) return rc;
     return has_abs ? bwd_dispatch<true>(a, (hipStream_t)stream) : bwd_dispatch<false>(a, (hipStream_t)stream);
 }
 
@@ -1304,15 +1280,9 @@ extern "C" int gsx_raster3d_sparse_bwd(
     GSX_REQUIRE(active_tiles && tile_offsets && tile_pixel_mask && tile_pixel_cumsum && pixel_map && means2d && conics
                 && colors && opacities && flatten_ids && render_alphas && last_ids && v_render_colors,
                 "gsx_raster3d_sparse_bwd: null input");
-    Raster3DArgs a{};
-    a.n_images = n_images; a.n_isects = n_isects; a.width = width; a.height = height;
-    a.tile_size = tile_size; a.tile_w = tile_w; a.tile_h = tile_h; a.cdim = cdim;
-    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
-    a.backgrounds = backgrounds; a.masks = masks; a.isect_offsets = tile_offsets; a.flatten_ids = flatten_ids;
-    a.render_alphas = const_cast<float *>(render_alphas); a.last_ids = const_cast<int32_t *>(last_ids);
-    a.v_render_colors = v_render_colors; a.v_render_alphas = v_render_alphas;
-    a.v_rows = v_rows; a.row_stride = row_stride;
-    a.sp_active_tiles = active_tiles; a.sp_pixel_mask = tile_pixel_mask; a.sp_pixel_cumsum = tile_pixel_cumsum;
-    a.sp_pixel_map = pixel_map; a.n_active = n_active; a.sp_words = words_per_tile;
+    Raster3DArgs a = raster3d_args(n_images, n_isects, cdim, width, height, tile_size, tile_w, tile_h, means2d, conics, colors,
+                                   opacities, backgrounds, masks, tile_offsets, flatten_ids, nullptr, render_alphas, last_ids);
+    raster3d_set_bwd(a, v_render_colors, v_render_alphas, v_rows, row_stride);
+    raster3d_set_sparse(a, active_tiles, tile_pixel_mask, tile_pixel_cumsum, pixel_map, n_active, words_per_tile);
     return has_abs ? bwd_dispatch<true>(a, (hipStream_t)stream) : bwd_dispatch<false>(a, (hipStream_t)stream);
 }

@@ -250,25 +250,17 @@ int raster3d_bwd_prepass_launch(const Raster3DArgs &a, hipStream_t stream)
     const uint32_t grid = ((a.seg_grid + 7u) / 8u) * 8u;
     if (grid == 0) return GSX_OK;
     const size_t smem = kBatch * (sizeof(StagedRow) + sizeof(float4));
-    if (a.nch <= 1) hipLaunchKernelGGL((raster3d_fwd_kernel<1, true>), dim3(grid), dim3(256), smem, stream, a);
-    else if (a.nch <= 2) hipLaunchKernelGGL((raster3d_fwd_kernel<2, true>), dim3(grid), dim3(256), smem, stream, a);
-    else if (a.nch <= 3) hipLaunchKernelGGL((raster3d_fwd_kernel<3, true>), dim3(grid), dim3(256), smem, stream, a);
-    else hipLaunchKernelGGL((raster3d_fwd_kernel<4, true>), dim3(grid), dim3(256), smem, stream, a);
+    with_channels4(a.nch, [&](auto ch) {
+        hipLaunchKernelGGL((raster3d_fwd_kernel<ch(), true>), dim3(grid), dim3(256), smem, stream, a);
+    });
     return check_launch("raster3d_bwd_prepass");
 }
 
 // one launch for the channel chunk described by a.ch_off / a.nch / a.first_chunk
 int raster3d_fwd_launch_chunk(const Raster3DArgs &a, hipStream_t stream)
 {
-    const uint32_t n = a.nch;
     if (raster3d_fwd_m_applies(a)) return raster3d_fwd_m_launch(a, stream); // 5 .. 32 channels: the render as a matrix product
-    if (n <= 1) return launch_fwd<1>(a, stream);
-    if (n <= 2) return launch_fwd<2>(a, stream);
-    if (n <= 3) return launch_fwd<3>(a, stream);
-    if (n <= 4) return launch_fwd<4>(a, stream);
-    if (n <= 8) return launch_fwd<8>(a, stream);
-    if (n <= 16) return launch_fwd<16>(a, stream);
-    return launch_fwd<32>(a, stream);
+    return with_channels(a.nch, [&](auto ch) { return launch_fwd<ch()>(a, stream); });
 }
 
 int raster3d_fwd_dispatch(Raster3DArgs a, hipStream_t stream)
@@ -306,12 +298,8 @@ extern "C" int gsx_raster3d_fwd(
     GSX_REQUIRE(n_isects == 0 || (means2d && conics && colors && opacities && flatten_ids),
                 "gsx_raster3d_fwd: null input");
     GSX_REQUIRE(isect_offsets != nullptr || n_images * tile_w * tile_h == 0, "gsx_raster3d_fwd: null isect_offsets");
-    Raster3DArgs a{};
-    a.n_images = n_images; a.n_isects = n_isects; a.width = width; a.height = height;
-    a.tile_size = tile_size; a.tile_w = tile_w; a.tile_h = tile_h; a.cdim = cdim;
-    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
-    a.backgrounds = backgrounds; a.masks = masks; a.isect_offsets = isect_offsets; a.flatten_ids = flatten_ids;
-    a.render_colors = render_colors; a.render_alphas = render_alphas; a.last_ids = last_ids;
+    Raster3DArgs a = raster3d_args(n_images, n_isects, cdim, width, height, tile_size, tile_w, tile_h, means2d, conics, colors,
+                                   opacities, backgrounds, masks, isect_offsets, flatten_ids, render_colors, render_alphas, last_ids);
     return raster3d_fwd_dispatch(a, (hipStream_t)stream);
 }
 
@@ -333,13 +321,8 @@ extern "C" int gsx_raster3d_sparse_fwd(
     GSX_REQUIRE(active_tiles && tile_offsets && tile_pixel_mask && tile_pixel_cumsum && pixel_map && render_colors
                 && render_alphas && last_ids, "gsx_raster3d_sparse_fwd: null layout / output");
     GSX_REQUIRE(n_isects == 0 || (means2d && conics && colors && opacities && flatten_ids), "gsx_raster3d_sparse_fwd: null input");
-    Raster3DArgs a{};
-    a.n_images = n_images; a.n_isects = n_isects; a.width = width; a.height = height;
-    a.tile_size = tile_size; a.tile_w = tile_w; a.tile_h = tile_h; a.cdim = cdim;
-    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
-    a.backgrounds = backgrounds; a.masks = masks; a.isect_offsets = tile_offsets; a.flatten_ids = flatten_ids;
-    a.render_colors = render_colors; a.render_alphas = render_alphas; a.last_ids = last_ids;
-    a.sp_active_tiles = active_tiles; a.sp_pixel_mask = tile_pixel_mask; a.sp_pixel_cumsum = tile_pixel_cumsum;
-    a.sp_pixel_map = pixel_map; a.n_active = n_active; a.sp_words = words_per_tile;
+    Raster3DArgs a = raster3d_args(n_images, n_isects, cdim, width, height, tile_size, tile_w, tile_h, means2d, conics, colors,
+                                   opacities, backgrounds, masks, tile_offsets, flatten_ids, render_colors, render_alphas, last_ids);
+    raster3d_set_sparse(a, active_tiles, tile_pixel_mask, tile_pixel_cumsum, pixel_map, n_active, words_per_tile);
     return raster3d_fwd_dispatch(a, (hipStream_t)stream);
 }

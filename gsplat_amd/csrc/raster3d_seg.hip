@@ -289,12 +289,8 @@ extern "C" int gsx_raster3d_fwd_seg(
     GSX_REQUIRE(n_isects == 0 || (means2d && conics && colors && opacities && flatten_ids), "gsx_raster3d_fwd_seg: null input");
     GSX_REQUIRE(isect_offsets != nullptr || n_images * tile_w * tile_h == 0, "gsx_raster3d_fwd_seg: null isect_offsets");
     hipStream_t s = (hipStream_t)stream;
-    Raster3DArgs a{};
-    a.n_images = n_images; a.n_isects = n_isects; a.width = width; a.height = height;
-    a.tile_size = tile_size; a.tile_w = tile_w; a.tile_h = tile_h; a.cdim = cdim;
-    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
-    a.backgrounds = backgrounds; a.masks = masks; a.isect_offsets = isect_offsets; a.flatten_ids = flatten_ids;
-    a.render_colors = render_colors; a.render_alphas = render_alphas; a.last_ids = last_ids;
+    Raster3DArgs a = raster3d_args(n_images, n_isects, cdim, width, height, tile_size, tile_w, tile_h, means2d, conics, colors,
+                                   opacities, backgrounds, masks, isect_offsets, flatten_ids, render_colors, render_alphas, last_ids);
     const uint32_t n_blocks = n_images * tile_w * tile_h;
     if (n_blocks == 0) return GSX_OK;
     const uint32_t nch_max = cdim > 32 ? 32 : cdim;
@@ -368,14 +364,9 @@ static int raster3d_bwd_seg_impl(
     GSX_REQUIRE(means2d && conics && colors && opacities && flatten_ids && render_alphas && last_ids && v_render_colors
                 && isect_offsets, "gsx_raster3d_bwd_seg: null input");
     hipStream_t s = (hipStream_t)stream;
-    Raster3DArgs a{};
-    a.n_images = n_images; a.n_isects = n_isects; a.width = width; a.height = height;
-    a.tile_size = tile_size; a.tile_w = tile_w; a.tile_h = tile_h; a.cdim = cdim;
-    a.means2d = means2d; a.conics = conics; a.colors = colors; a.opacities = opacities;
-    a.backgrounds = backgrounds; a.masks = masks; a.isect_offsets = isect_offsets; a.flatten_ids = flatten_ids;
-    a.render_alphas = const_cast<float *>(render_alphas); a.last_ids = const_cast<int32_t *>(last_ids);
-    a.v_render_colors = v_render_colors; a.v_render_alphas = v_render_alphas;
-    a.v_rows = v_rows; a.row_stride = row_stride;
+    Raster3DArgs a = raster3d_args(n_images, n_isects, cdim, width, height, tile_size, tile_w, tile_h, means2d, conics, colors,
+                                   opacities, backgrounds, masks, isect_offsets, flatten_ids, nullptr, render_alphas, last_ids);
+    raster3d_set_bwd(a, v_render_colors, v_render_alphas, v_rows, row_stride);
     a.ch_off = 0; a.nch = cdim; a.first_chunk = 1;
     const uint32_t n_blocks = n_images * tile_w * tile_h;
     if (n_blocks == 0) return GSX_OK;
