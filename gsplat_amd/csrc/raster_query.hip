@@ -29,7 +29,7 @@ struct QueryArgs {
     float *alphas;   // mode 0: [I,H,W]
     int32_t *ids;    // mode 1/2: [I,H,W,K]  (mode 1: pre-filled with -1 by the caller)
     float *weights;  // mode 1/2: [I,H,W,K]  (mode 1: pre-filled with 0)
-    unsigned long long *stats; // mode 3: [4] work counters, added to with atomics (see gsx_raster3d_pair_stats)
+    unsigned long long *stats; // mode 3: [5] work counters, added to with atomics (see gsx_raster3d_pair_stats)
 };
 
 constexpr int kQBatch = 256;
@@ -162,6 +162,7 @@ __global__ void __launch_bounds__(256) raster3d_query_kernel(const QueryArgs a)
         //     the one that saturates the pixel; no culling) - the reference kernel's work, SURVEY.md 8(d) "pairs"
         // [1] lane evaluations of this backend: 64 x (wave, Gaussian) pairs that survive the wave-level culling
         // [2] of those, lanes whose pixel was still open   [3] contributing pairs (alpha >= 1/255, before saturation)
+        // [4] of [1], the evaluations of (wave, Gaussian) pairs in which no lane passes the alpha test
         if (inside && !done) walked = (uint32_t)(range_end - range_start);
         unsigned long long v0 = inside ? walked : 0u, v2 = lane_evals, v3 = inside ? count : 0u;
         for (int o = 32; o >= 1; o >>= 1) {
@@ -307,7 +308,7 @@ extern "C" int gsx_raster3d_top_contributing(const float *means2d, const float *
 }
 
 // Instrumentation (not a reference op): how much work the compositing pass of this scene is. Replays the forward walk and
-// adds four counters to stats[0..3] (zeroed by the caller; see the kernel): bench.py prices the vector ALU with them
+// adds five counters to stats[0..4] (zeroed by the caller; see the kernel): bench.py prices the vector ALU with them
 // (pairs x (14 + 2 D) flop against the fp32 peak).
 extern "C" int gsx_raster3d_pair_stats(const float *means2d, const float *conics, const float *opacities,
                                        const int32_t *isect_offsets, const int32_t *flatten_ids, uint32_t n_images,

@@ -875,7 +875,7 @@ int gsx_surfel_post_bwd(const float *colors, const float *alphas, const float *n
 
 /* Instrumentation (no reference counterpart): work counters of the compositing pass, for the vector-ALU roofline of
  * bench.py (pairs x (14 + 2 D) flop against the fp32 peak). Replays the forward walk of
- * gsx_raster3d_fwd and ADDS to stats[0..3] (caller zeroes them):
+ * gsx_raster3d_fwd and ADDS to stats[0..4] (caller zeroes them):
  *   [0] (pixel, Gaussian) pairs a per-pixel serial walk evaluates (the reference kernel's work: every list entry up to
  *       and including the one that saturates the pixel), [1] lane evaluations of this backend (64 x (wave, Gaussian) pairs
  *       surviving the wave-level culling), [2] of those the lanes whose pixel was still open, [3] contributing pairs,

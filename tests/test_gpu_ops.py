@@ -872,8 +872,9 @@ def test_sh_half_coefficients(G, O, split):
 
 def test_rasterize_to_indices_matches_oracle(G, O):
     """rasterize_to_indices_in_range{,_2dgs}: contributing (gaussian, pixel, image) triples in the reference's order
-    (pixel-major, list order). Full range vs the oracle; a split range chained through the transmittance must give the
-    same set (the reference's torch rasterizer relies on that: _torch_impl.py:871-905)."""
+    (pixel-major, list order). Full range from T0 = 1 vs the oracle. Windows of the lists chained through the transmittance
+    are checked in tests/test_gpu_query.py against a walk of the same window - NOT against the full range: the stop is per
+    call (in the reference too), so a pixel that saturates inside one window starts the next one afresh."""
     sc, W, H = make_scene(N=1500, C=2, width=72, height=56, seed=8)
     a, rad, m2, d, con, op = _project_scene(G, sc, W, H)
     tw, th = math.ceil(W / 16), math.ceil(H / 16)
