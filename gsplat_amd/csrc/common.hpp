@@ -82,11 +82,6 @@ __device__ __forceinline__ float dpp_ror8(float x)
 // Sum over each row of 16 lanes; every lane of the row ends up with the row sum.
 __device__ __forceinline__ float row16_sum(float x)
 {
-#if defined(GSX_SAFE_REDUCE) && GSX_SAFE_REDUCE
-#pragma unroll
-    for (int o = 8; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-#endif
     x += dpp_f32<0xB1>(x);  // quad_perm [1,0,3,2]
     x += dpp_f32<0x4E>(x);  // quad_perm [2,3,0,1]
     x += dpp_f32<0x141>(x); // row_half_mirror
@@ -110,18 +105,12 @@ __device__ __forceinline__ float wave_sum(float x)
 // row sums, then row_bcast15 (lane 15 of the previous row -> rows 1 and 3), then row_bcast31 (lane 31 -> rows 2, 3).
 __device__ __forceinline__ float wave_sum_last_row(float x)
 {
-#if defined(GSX_SAFE_REDUCE) && GSX_SAFE_REDUCE
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-#else
     x = row16_sum(x);
     // all rows enabled (lets the compiler fuse v_add_f32_dpp): rows without a source read 0 (old = 0); rows 1 and
     // 2 end up with partial sums nobody reads, row 3 = (r2 + r3) + (r0 + r1).
     x += dpp_f32<0x142>(x); // row_bcast15: lane 15 of the previous row
     x += dpp_f32<0x143>(x); // row_bcast31: lane 31 -> rows 2 and 3
     return x;
-#endif
 }
 
 // Reduce FOUR per-lane values over the wave in one go ("reduce-scatter"): on return every lane of
@@ -130,20 +119,8 @@ __device__ __forceinline__ float wave_sum_last_row(float x)
 // 64-lane reductions cost 3 swaps + 3 adds + 4 DPP adds instead of 4 x 6 DPP adds.
 //   permlane16_swap(x, y): odd rows of x <-> even rows of y      (ISA V_PERMLANE16_SWAP_B32)
 //   permlane32_swap(x, y): lanes 32-63 of x <-> lanes 0-31 of y  (ISA V_PERMLANE32_SWAP_B32)
-// Build with -DGSX_SAFE_REDUCE=1 to get a plain __shfl_xor version (debug / A-B reference).
 __device__ __forceinline__ float wave_sum4_scatter(float a, float b, float c, float d)
 {
-#if defined(GSX_SAFE_REDUCE) && GSX_SAFE_REDUCE
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        a += __shfl_xor(a, o);
-        b += __shfl_xor(b, o);
-        c += __shfl_xor(c, o);
-        d += __shfl_xor(d, o);
-    }
-    const int row = (int)(threadIdx.x & 63u) >> 4;
-    return row == 0 ? a : (row == 1 ? b : (row == 2 ? c : d));
-#else
     const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     const float P = __uint_as_float(p[0]) + __uint_as_float(p[1]); // rows: a01, b01, a23, b23
     const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(c), __float_as_uint(d), false, false);
@@ -151,28 +128,18 @@ __device__ __forceinline__ float wave_sum4_scatter(float a, float b, float c, fl
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(P), __float_as_uint(Q), false, false);
     const float R = __uint_as_float(r[0]) + __uint_as_float(r[1]); // rows: a, b, c, d (per column)
     return row16_sum(R);
-#endif
 }
 
 // The cross-row half of wave_sum4_scatter: lane (row r, column c) returns the sum over the four 16-lane rows, taken at
 // column c, of value r of (a, b, c, d) - i.e. four independent 4-way sums per column in 3 swaps + 3 adds.
 __device__ __forceinline__ float rows_sum4_scatter(float a, float b, float c, float d)
 {
-#if defined(GSX_SAFE_REDUCE) && GSX_SAFE_REDUCE
-    a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
-    b += __shfl_xor(b, 16); b += __shfl_xor(b, 32);
-    c += __shfl_xor(c, 16); c += __shfl_xor(c, 32);
-    d += __shfl_xor(d, 16); d += __shfl_xor(d, 32);
-    const int row = (int)(threadIdx.x & 63u) >> 4;
-    return row == 0 ? a : (row == 1 ? b : (row == 2 ? c : d));
-#else
     const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     const float P = __uint_as_float(p[0]) + __uint_as_float(p[1]); // rows: a01, b01, a23, b23
     const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(c), __float_as_uint(d), false, false);
     const float Q = __uint_as_float(q[0]) + __uint_as_float(q[1]); // rows: c01, d01, c23, d23
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(P), __float_as_uint(Q), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);          // rows: a, b, c, d (per column)
-#endif
 }
 
 // Order LDS traffic between the lanes of ONE wave (data handed from lane to lane through a wave-private LDS region).
@@ -187,11 +154,6 @@ __device__ __forceinline__ int wave_max_i32(int x)
 {
     // butterfly with DPP inside rows, then readlane across rows
     auto step = [](int v, int o) { return v > o ? v : o; };
-#if defined(GSX_SAFE_REDUCE) && GSX_SAFE_REDUCE
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = step(x, __shfl_xor(x, o));
-    return x;
-#endif
     x = step(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false));
     x = step(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));
     x = step(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false));

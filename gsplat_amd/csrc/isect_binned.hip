@@ -97,7 +97,6 @@ struct BinArgs {
     uint64_t *keys_out;
     int32_t *vals_out;
     uint2 *bucketed;
-    uint32_t dbg; // GSX_ISECT_DBG ablation bits (timing experiments only; outputs are wrong when set)
     uint32_t sort_int; // GSX_ISECT_SORT=int: every list on the integer network
 };
 
@@ -274,10 +273,10 @@ __global__ void __launch_bounds__(kRowThreads) bin_rect_kernel(const BinArgs a)
                 const uint32_t w = bx1 - bx0, h = by1 - by0;
                 const bool one   = w <= sh.kx && h <= sh.ky;
                 const int slabs  = p.ellipse ? min(p.x1 - p.x0, p.y1 - p.y0) : 1;
-                if (one && slabs <= (int)(((a.dbg >> 16) & 15u) ? ((a.dbg >> 16) & 15u) : (uint32_t)kInlineSlabs) && !(a.dbg & 16u)) {
+                if (one && slabs <= kInlineSlabs) {
                     const int cx0 = (int)(bx0 * sh.bw), cy0 = (int)(by0 * sh.bh);
                     rec = make_record(block_mask(p, g.tile_size, g.tile_w, cx0, cy0, cx0 + (int)W, cy0 + (int)Hh, W, col, tmask), bx0, by0, dbits[u], g, sh, s_hist);
-                } else if (!(a.dbg & 64u)) {
+                } else {
                     // park the prepared walk and push its units at once: in the usual case one barrier separates this from the drain
                     units[u] = one ? 1u : ((w + sh.kx - 1) / sh.kx) * ((h + sh.ky - 1) / sh.ky);
                     const int32_t m = atomicAdd(&s_mn, 1);
@@ -302,14 +301,14 @@ __global__ void __launch_bounds__(kRowThreads) bin_rect_kernel(const BinArgs a)
                     }
                 }
             }
-            if (now && !(a.dbg & 32u)) {
+            if (now) {
                 a.b.row_rec[r] = rec;
                 if (a.tiles_per_gauss && ((rec.z >> 16) & 3u) != kRecBig) a.tiles_per_gauss[r] = __popc(rec.x) + __popc(rec.y);
             }
         }
         // rounds of { drain the queue together } / (rare) { park and push what found no room }
         for (bool more = __syncthreads_or(left);;) {
-            const int32_t n_q = (a.dbg & 256u) ? 0 : min(s_qn, s_qlim);
+            const int32_t n_q = min(s_qn, s_qlim);
             for (int32_t k = (int32_t)threadIdx.x; k < n_q; k += kRowThreads) {
                 const uint32_t pr  = s_q[k];
                 const uint32_t *rw = s_row[pr & 511u];
@@ -320,7 +319,7 @@ __global__ void __launch_bounds__(kRowThreads) bin_rect_kernel(const BinArgs a)
                 const uint32_t wb = (w + sh.kx - 1) / sh.kx, idx = pr >> 9;
                 const uint32_t bbx = bx0 + (idx % wb) * sh.kx, bby = by0 + (idx / wb) * sh.ky;
                 const int cx0 = (int)(bbx * sh.bw), cy0 = (int)(bby * sh.bh);
-                const uint64_t M = (a.dbg & 512u) ? 1ull : block_mask(p, g.tile_size, g.tile_w, cx0, cy0, cx0 + (int)W, cy0 + (int)Hh, W, col, tmask);
+                const uint64_t M = block_mask(p, g.tile_size, g.tile_w, cx0, cy0, cx0 + (int)W, cy0 + (int)Hh, W, col, tmask);
                 const int64_t r  = base + slot;
                 if (one) {
                     a.b.row_rec[r] = make_record(M, bbx, bby, rw[4], g, sh, s_hist);
@@ -467,7 +466,6 @@ __device__ __forceinline__ void bn_deal(const BinArgs &a, const BinShape<FIXED> 
         used &= used - 1u;
         const uint32_t i = k % sh.kx, j = k / sh.kx;
         const int32_t slot = atomicAdd(&s_cur[(by0 + j) * a.g.bins_x + bx0 + i], 1);
-        if (a.dbg & 8u) continue;
         a.b.e_pair[slot] = make_uint2(rec.w, row);
         a.b.e_mask[slot] = (uint16_t)rec_bin_mask(M, sh, i, j);
     }
@@ -480,7 +478,7 @@ __global__ void __launch_bounds__(kRowThreads) bin_scatter_kernel(const BinArgs 
     const BinGeom &g = a.g;
     const BinShape<FIXED> sh(g);
     const uint32_t per_xcd = gridDim.x / 8u;
-    const uint32_t chunk   = (a.dbg & 4096u) ? blockIdx.x : (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
+    const uint32_t chunk   = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
     if (chunk >= g.n_chunks) return;
     int64_t lo, hi;
     uint32_t img;
@@ -635,7 +633,7 @@ __global__ void __launch_bounds__(1024) bin_sort_kernel(const BinArgs a)
         // deal every entry to the lists of the tiles in its mask (LDS cursor per tile). (Round 5: requesting several trips'
         // entries together, or a group ahead, changes nothing - 70.6 .. 71.9 us for 1 / 2 / 4 / 8 trips -: with eight waves per
         // SIMD the other waves cover a wave's round trips; the group held ahead costs registers and a workgroup per CU, 77 us.)
-        for (int32_t e = e0 + (int32_t)threadIdx.x; e < e1 && !(a.dbg & 2u); e += n_thr) {
+        for (int32_t e = e0 + (int32_t)threadIdx.x; e < e1; e += n_thr) {
             uint32_t m = (uint32_t)a.b.e_mask[e] & bmask;
             if (m == 0u) continue;
             const uint2 pr     = a.b.e_pair[e];
@@ -658,8 +656,7 @@ __global__ void __launch_bounds__(1024) bin_sort_kernel(const BinArgs a)
             const uint64_t pad = as_int ? kBtPadInt : kBtPadF64;
             for (int i = n + lane; i < (1 << lp); i += 64) sw[bt_phys(i)] = pad;
             wave_lds_sync();
-            if (a.dbg & 1u) {
-            } else if (as_int) bt_sort_int<64>(sw, lp, lane, [] { wave_lds_sync(); });
+            if (as_int) bt_sort_int<64>(sw, lp, lane, [] { wave_lds_sync(); });
             else bt_sort_f64<64>(sw, lp, lane, [] { wave_lds_sync(); });
             const int64_t off = s_goff[wave];
             const uint64_t hi = s_hi[wave];
@@ -862,9 +859,9 @@ extern "C" int gsx_isect_binned_should_try(int64_t rows, uint32_t n_images, uint
 }
 static int binned_decide(int64_t rows, uint32_t n_images, uint32_t tile_w, uint32_t tile_h, int packed, bool consume)
 {
-    // GSX_ISECT_PATH = binned | legacy forces the choice (tests, A/B); GSX_ISECT_LEGACY is the older spelling of "legacy"
+    // GSX_ISECT_PATH = binned | legacy forces the choice (tests, A/B)
     const char *force = getenv("GSX_ISECT_PATH");
-    if (getenv("GSX_ISECT_LEGACY") || (force && force[0] == 'l')) return 0;
+    if (force && force[0] == 'l') return 0;
     if (packed && n_images != 1) return 0; // packed rows: per-image row counts live on the device
     if (n_images < 1 || tile_w < 1 || tile_h < 1 || rows < 0) return 0;
     if (rows % n_images != 0) return 0;
@@ -909,15 +906,13 @@ static int binned_setup(const char *fn, BinArgs &a, int64_t rows, uint32_t n_ima
                 (long long)rows, n_images);
     GSX_REQUIRE(bin_geometry(a.g, rows, n_images, tile_size, tile_w, tile_h, bin_cap_entries(rows)),
                 "%s: %u images x %u x %u tiles not supported", fn, n_images, tile_w, tile_h);
-    if (const char *e = getenv("GSX_ISECT_DBG")) a.dbg = (uint32_t)atoi(e);
     a.sort_int = bitonic_f64_enabled() ? 0u : 1u;
     // skew abort: 3/4 of the sort arena's words (a c3 bin of 4x2 tiles holds ~1400 entries, its longest ~1700); not when the
-    // path was forced (tests drive the big-list code with it); GSX_ISECT_BIN_SKEW overrides (0 = never)
+    // path was forced (tests drive the big-list code with it)
     {
-        const char *force = getenv("GSX_ISECT_PATH"), *sk = getenv("GSX_ISECT_BIN_SKEW");
+        const char *force = getenv("GSX_ISECT_PATH");
         a.g.skew_cap = (force && force[0] == 'b') ? 0 : (int32_t)(kArenaPerWave * (int)(a.g.bw * a.g.bh) * 3 / 4);
         a.g.skew_ratio = (force && force[0] == 'b') ? 0 : 4;
-        if (sk) { a.g.skew_cap = atoi(sk); a.g.skew_ratio = a.g.skew_cap > 0 ? 4 : 0; }
     }
     unsigned char *base = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
     if (ws == nullptr || (base - reinterpret_cast<unsigned char *>(ws)) + bin_layout(a.g, base, &a.b) > ws_bytes) {

@@ -55,7 +55,7 @@ inline FusedGeom fused_geometry(int64_t rows, uint32_t n_images, uint32_t tile_s
     // crowded regions run several times longer), so up to 768 chunks of >= 4096 rows while the [chunk][tile] table stays
     // small; very large inputs (c4: 16 M random rows) keep one chunk per CU - more only lengthens the table.
     // measured (count + emit+sort, ms): garden x25 256 chunks 0.423, 384 0.344, 768 0.310, 2048 0.310; c4 256 2.44, 768 2.60
-    // A/B: GSX_FUSED_WG = "<threads>x<chunks>" (e.g. 512x512); 512-thread workgroups (two per CU) gained nothing
+    // 512-thread workgroups (two per CU) gained nothing
     int64_t kMaxChunks = rows <= 6000000 ? 768 : 256;
     // "the table must stay small": 768 chunks were measured at 8160 tiles (25 MB of table). A larger tile grid keeps the table
     // below that budget instead of growing it threefold (4K image, 32 k tiles, 3 M rows: 95 MB and a 3x longer column scan).
@@ -65,11 +65,6 @@ inline FusedGeom fused_geometry(int64_t rows, uint32_t n_images, uint32_t tile_s
         if (kMaxChunks > 256 && by_budget < kMaxChunks) kMaxChunks = by_budget < 256 ? 256 : by_budget;
     }
     g.threads = 1024;
-    static const char *const wg_env = getenv("GSX_FUSED_WG");
-    if (wg_env) {
-        unsigned t = 0, c = 0;
-        if (sscanf(wg_env, "%ux%u", &t, &c) == 2 && (t == 512 || t == 1024) && c >= 64 && c <= 2048) { g.threads = t; kMaxChunks = c; }
-    }
     constexpr int64_t kMinRows = 4096;
     const int64_t max_cpi = kMaxChunks / g.n_images > 0 ? kMaxChunks / g.n_images : 1;
     int64_t cpi = (g.rows_per_image + kMinRows - 1) / kMinRows;

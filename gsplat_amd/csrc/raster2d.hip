@@ -491,9 +491,6 @@ __global__ void __launch_bounds__(256) raster2d_bwd_kernel(const Raster2DArgs a)
 #ifndef GSX_BWD2_H_WAVES
 #define GSX_BWD2_H_WAVES 4
 #endif
-#ifndef GSX_BWD2_W_STAGE_AHEAD
-#define GSX_BWD2_W_STAGE_AHEAD 1
-#endif
 template <int CH>
 struct Bwd2WCfg {
     static constexpr int K     = CH + 15;

@@ -303,9 +303,10 @@ __device__ __forceinline__ bool tile_context_ordered(const Raster3DArgs &a, uint
     return true;
 }
 
-// Wide colour rows (5 .. 32 channels per launch, 16 x 16 tiles, no absgrad) on the matrix cores: raster3d_bwd_m.hip.
-// GSX_RASTER3D_BWD_WIDE=r keeps the reduction kernel.
-bool raster3d_bwd_m_applies(const Raster3DArgs &a, bool has_abs);
+// Which backward kernel takes a chunk of nch channels (raster3d_bwd.hip): the reduction kernel, variant T, variant W, or, for
+// wide colour rows (5 .. 32 channels per launch, 16 x 16 tiles, no absgrad), the matrix cores (raster3d_bwd_m.hip).
+enum class BwdKernel { R, T, W, M };
+BwdKernel raster3d_bwd_kernel(uint32_t tile_size, uint32_t nch, bool has_abs);
 int raster3d_bwd_m_launch(const Raster3DArgs &a, hipStream_t stream);
 
 // thread -> pixel inside the tile.
@@ -353,84 +354,36 @@ __device__ __forceinline__ float staged_e_offset(const float4 &ga, const float2 
     return fmaf(dx, fmaf(-gb.x, dy, -ga.w * dx), fmaf(-gb.y * dy, dy, ga.z));
 }
 
-// ---- staged form, tile-centre polynomial ("e-form"; raster3d_fwd.hip and variant T of raster3d_bwd.hip) -------------------
-// With a = mean - c (c = centre of the tile) and a lane's pixel at u = pixel - c (|u|, |v| <= 7.5, exact in fp32):
-//   q(u, v) = A (a.x - u)^2 + B (a.x - u)(a.y - v) + C (a.y - v)^2
-//           = q0 - u gu - v gv + A u^2 + B u v + C v^2,   q0 = q(0, 0),  gu = 2 A a.x + B a.y,  gv = B a.x + 2 C a.y
-// so the exponent of alpha = exp2(lo - q) is
-//   e(u, v) = e0 + u (gu + nA u + nB v) + v (gv + nC v),   e0 = lo - q0,  (nA, nB, nC) = -(A, B, C)
-// i.e. FIVE fmas per (pixel, Gaussian) instead of 2 subtractions + 5 for q + 1 for lo - q; e0 / gu / gv are formed once
-// per (tile, Gaussian) by the staging thread. sigma < 0  <=>  q < 0  <=>  e > lo. Conditioning: the terms that cancel are
-// bounded by |u| (|gu| + ...) with |u| <= 7.5 and, for the Gaussians that can pass the alpha test at all, |a| <= 7.5 +
-// extent: a few hundred at most for the tightest footprint (eps2d = 0.3) -> ~2e-5 absolute on e, ~1.5e-5 relative on alpha
-// (the tolerance of the parity tests is 1e-4 .. 1e-3; variant T's moments about the tile centre are conditioned alike).
-//
-// The sigma < 0 test. Mathematically e <= lo wherever the conic is positive definite, with equality at the mean; in fp32 the
-// cancelling terms leave e a few 1e-5 ABOVE lo for a pixel centre that sits (almost) exactly on the mean - and `e > lo` then
-// dropped the Gaussian at the one pixel where it weighs most (found by the reference's own
-// test_rasterize_num_contributing_gaussians, whose means are pixel centres). The staged reject level is therefore
-// lo + kLoMargin: a pair is rejected only where sigma < -kLoMargin / log2(e) ~ -8.5e-5, which a valid conic never reaches and
-// which costs an invalid one nothing that matters (alpha within 1.0001 of the opacity). Readers that need lo itself (the
-// backward's 1 / opacity) subtract the margin again.
-#ifndef GSX_DFORM
-#define GSX_DFORM 1 // 1: every kernel evaluates the exponent from the offset (stage_gaussian_f / staged_f below): e == lo at the mean
-#endif
-constexpr float kLoMargin = GSX_DFORM ? 0.0f : 1.220703125e-4f; // 2^-13 for the polynomial; the offset form needs none
+// ---- staged form of the tile kernels (raster3d_fwd*.hip, raster_indices.hip, variants T / W and the matrix-core backward) ------
+// With a = mean - c (c = centre of the tile) and a lane's pixel at (u, v) = pixel - c (|u|, |v| <= 7.5, exact in fp32) the
+// exponent of alpha = exp2(e) is evaluated the way the reference does, from the offset d = a - (u, v) = mean - pixel:
+//   e = lo - (A dx^2 + B dx dy + C dy^2) = fma(dx, fma(nB, dy, nA dx), fma(nC dy, dy, lo)),   (nA, nB, nC) = -(A, B, C)
+// whose error is a few ulp of the RESULT (~3e-6 at p99.99 on log2(alpha)): the reference's own forward test compares the
+// rasterizer with its PyTorch restatement at atol 1e-5 (tests/test_basic.py:2639, torch.testing.assert_close defaults).
+// sigma < 0  <=>  q < 0  <=>  e > lo, and e == lo exactly at the mean: a pixel centre that sits on the mean is never rejected
+// (the reference's test_rasterize_num_contributing_gaussians, whose means are pixel centres), so the reject level is lo itself.
+// The BACKWARD kernels evaluate the same function through the same instructions (stage_gaussian_f / staged_f): a pair is blended
+// by the backward iff the forward blended it - with another evaluation of the exponent in the backward, a pair within 1.5e-5 of
+// the 1/255 test was taken by one and not by the other (6 of 369 k rows of v_means2d off by up to 6e-3 in the reference's
+// test_rasterize_to_pixels). Their moments stay in the tile-centre frame (u, v); one wave per tile (variant W) shares dx / dy
+// between the four pixels of a lane.
 struct StagedRow { // one staged Gaussian in LDS: 48 bytes, read as b128 + b128 + b64 from ONE address register
-    v4f p0;        // e0, gu, gv, lo + kLoMargin
+    v4f p0;        // ax, ay (mean - tile centre), lo (base of the exponent), lo (reject level: e > lo <=> sigma < 0)
     v4f p1;        // nA, nB, nC, colour 2
     v4f p2;        // colour 0, colour 1, colour 3, -
 };
-__device__ __forceinline__ void stage_gaussian_e(float ax, float ay, float opac, float ca, float cb, float cc, v4f &p0,
-                                                 float &nA, float &nB, float &nC)
-{
-    const float lo = opac > 0.0f ? __log2f(opac) : -INFINITY; // opac <= 0 (or NaN) can never pass the alpha test
-    const float A = 0.5f * kLog2e * ca, B = kLog2e * cb, C = 0.5f * kLog2e * cc;
-    const float q0 = fmaf(ax, fmaf(A, ax, B * ay), C * ay * ay);
-    p0 = v4f{lo - q0, fmaf(2.0f * A, ax, B * ay), fmaf(B, ax, 2.0f * C * ay), lo + kLoMargin};
-    nA = -A; nB = -B; nC = -C;
-}
-__device__ __forceinline__ float staged_e(const v4f &p0, float nA, float nB, float nC, float u, float v)
-{
-    const float t1 = fmaf(nB, v, fmaf(nA, u, p0.y));
-    const float t2 = fmaf(nC, v, p0.z);
-    return fmaf(v, t2, fmaf(u, t1, p0.x));
-}
-
-// ---- staged form of the FORWARD-side kernels ("d-form": raster3d_fwd*.hip, raster_indices.hip) ---------------------------------
-// The tile-centre polynomial costs five fmas per (pixel, Gaussian) but loses digits where its terms cancel: |e - exact| reaches
-// ~2e-5 (p99.99) on log2(alpha), 1.5e-5 relative on alpha - which the REFERENCE'S OWN forward test does not allow: it compares
-// the rasterizer with its PyTorch restatement at atol 1e-5 (tests/test_basic.py:2639, torch.testing.assert_close defaults), and
-// over the shim 23 of 2.4 M colour values missed that by up to 0.41e-5 (profiles/r10_reference_suite.txt). The forward kernels
-// therefore evaluate the exponent the way the reference does, from the offset d = mean - pixel (two subtractions more per pair):
-//   e = lo - (A dx^2 + B dx dy + C dy^2) = fma(dx, fma(nB, dy, nA dx), fma(nC dy, dy, lo))
-// whose error is a few ulp of the RESULT (~3e-6 at p99.99). e == lo exactly at the mean, so the sigma < 0 test needs no margin.
-// The BACKWARD kernels evaluate the same function through the same instructions (stage_gaussian_f / staged_f): a pair is blended
-// by the backward iff the forward blended it - with the polynomial in the backward and the offset form in the forward a pair
-// within 1.5e-5 of the 1/255 test was taken by one and not by the other (6 of 369 k rows of v_means2d off by up to 6e-3 in the
-// reference's test_rasterize_to_pixels). Their moments stay in the tile-centre frame (u, v); one wave per tile (variant W)
-// shares dx / dy between the four pixels of a lane, so the offset form costs it 18 instructions where the polynomial took 20.
-// GSX_DFORM=0 builds the polynomial into every kernel again (A/B: no measurable difference at c3, profiles/r10_ab.md).
 __device__ __forceinline__ void stage_gaussian_f(float ax, float ay, float opac, float ca, float cb, float cc, v4f &p0,
                                                  float &nA, float &nB, float &nC)
 {
-#if GSX_DFORM
     const float lo = opac > 0.0f ? __log2f(opac) : -INFINITY; // opac <= 0 (or NaN) can never pass the alpha test
-    p0 = v4f{ax, ay, lo, lo}; // mean - tile centre | base of the exponent | reject level (e > lo <=> sigma < 0)
+    p0 = v4f{ax, ay, lo, lo};
     nA = -0.5f * kLog2e * ca; nB = -kLog2e * cb; nC = -0.5f * kLog2e * cc;
-#else
-    stage_gaussian_e(ax, ay, opac, ca, cb, cc, p0, nA, nB, nC);
-#endif
 }
 // (u, v) = pixel centre - tile centre
 __device__ __forceinline__ float staged_f(const v4f &p0, float nA, float nB, float nC, float u, float v)
 {
-#if GSX_DFORM
     const float dx = p0.x - u, dy = p0.y - v;
     return fmaf(dx, fmaf(nB, dy, nA * dx), fmaf(nC * dy, dy, p0.z));
-#else
-    return staged_e(p0, nA, nB, nC, u, v);
-#endif
 }
 
 // ---- wave-level culling -------------------------------------------------------------------------
@@ -475,7 +428,7 @@ __device__ __forceinline__ WaveRect wave_pixel_rect(bool inside, float px, float
     return r;
 }
 
-// Second, exact stage of the wave-level culling (for the kernels that stage the e-form, StagedRow above): the minimum of the
+// Second, exact stage of the wave-level culling (for the kernels that stage a StagedRow, above): the minimum of the
 // exponent's quadratic q over the wave's pixel rectangle, against the level where alpha = exp2(lo - q) drops below 1/255.
 // The axis-aligned box of cull_half_extent() lets through (wave, Gaussian) pairs whose ellipse misses the rectangle
 // diagonally - 13 % of the surviving pairs on c3 had no lane that passes the alpha test (r05 counters). q is convex, so its

@@ -300,21 +300,12 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
 // Tunables (A/B builds: make SUFFIX=_x EXTRA=-DGSX_BWD_T_...=..; measured on c3, MI355X, profiles/r04_ab_variant_t.md).
 // The defaults keep a workgroup at 30.4 KiB of LDS and <= 102 VGPRs, i.e. 5 workgroups per CU: occupancy and batch length
 // pull in opposite directions (BATCH 128 / 144 / 160 -> 533 / 526 / 572 us: 160 drops to 4 workgroups per CU).
-#ifndef GSX_RASTER3D_BWD_DEFAULT // 't': variant T, 'w': variant W (one wave per tile, below); GSX_RASTER3D_BWD=r|t|w at run time
-#define GSX_RASTER3D_BWD_DEFAULT 'w'
-#endif
 #ifndef GSX_BWD_T_BATCH
 #define GSX_BWD_T_BATCH 128
 #endif
 #ifndef GSX_BWD_T_WROW // 176 / 20: conflict-free b128 reads; 132 / 16: 2-way conflicts but 5.6 KiB less LDS per workgroup
 #define GSX_BWD_T_WROW 132
 #define GSX_BWD_T_WGRP 16
-#endif
-// GSX_BWD_T_PRIVATE=1: one accumulator table PER WAVE, added to with plain LDS read-modify-write, instead of one per workgroup
-// hit with ds_add_f32: on gfx950 a float LDS atomic retires ~0.75 lanes per cycle and CU - 28x slower than an integer one
-// or a plain write (tools/issue_rate.hip) - and variant T issues 72 of them per turn of 8 Gaussians.
-#ifndef GSX_BWD_T_PRIVATE
-#define GSX_BWD_T_PRIVATE 0
 #endif
 #ifndef GSX_BWD_T_WAVES // waves per SIMD the register allocation aims at
 #define GSX_BWD_T_WAVES 5
@@ -328,9 +319,8 @@ struct BwdTCfg {
     static constexpr int SLOTS = 8;                // Gaussians per turn
     static constexpr int WROW  = GSX_BWD_T_WROW;   // floats per slot: 8 pixel rows x WGRP
     static constexpr int WGRP  = GSX_BWD_T_WGRP;   // floats per row of 8 pixels: 8 x (fac, w) + 4 (bank spread)
-    static constexpr int NACC  = GSX_BWD_T_PRIVATE ? 4 : 1; // accumulator tables
     static constexpr size_t stage_bytes =
-        (size_t)BATCH * (sizeof(StagedRow) + sizeof(float4) + sizeof(int32_t) * 2 + sizeof(float) * KP * NACC);
+        (size_t)BATCH * (sizeof(StagedRow) + sizeof(float4) + sizeof(int32_t) * 2 + sizeof(float) * KP);
     static constexpr size_t smem = stage_bytes + sizeof(float) * (4 * SLOTS * WROW);
 };
 
@@ -348,12 +338,12 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
     static_assert(CH <= 4, "cotangent rows are staged as float4");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    StagedRow *s_st  = reinterpret_cast<StagedRow *>(smem_raw);    // tile-centre polynomial of the exponent + colours (raster3d.hpp)
+    StagedRow *s_st  = reinterpret_cast<StagedRow *>(smem_raw);    // staged offset form of the exponent + colours (raster3d.hpp)
     float4 *s_cull   = reinterpret_cast<float4 *>(s_st + BATCH);   // mean - tile centre, half extents of alpha >= 1/255
     int32_t *s_id    = reinterpret_cast<int32_t *>(s_cull + BATCH);
     int32_t *s_touch = s_id + BATCH;
-    float *s_acc     = reinterpret_cast<float *>(s_touch + BATCH); // [NACC][BATCH][KP]: colours | S0 Su Sv Suu Suv Svv
-    float *s_w       = s_acc + Cfg::NACC * BATCH * KP;             // [4 waves][SLOTS][WROW]
+    float *s_acc     = reinterpret_cast<float *>(s_touch + BATCH); // [BATCH][KP]: colours | S0 Su Sv Suu Suv Svv
+    float *s_w       = s_acc + BATCH * KP;                         // [4 waves][SLOTS][WROW]
 
     TileCtx tc;
     uint32_t seg_item = 0;
@@ -441,9 +431,7 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
     }
     for (int s = (int)tid; s < BATCH; s += (int)blockDim.x) {
 #pragma unroll
-        for (int w = 0; w < Cfg::NACC; ++w)
-#pragma unroll
-            for (int k = 0; k < KP; ++k) s_acc[(w * BATCH + s) * KP + k] = 0.0f;
+        for (int k = 0; k < KP; ++k) s_acc[s * KP + k] = 0.0f;
         s_touch[s] = 0;
     }
 
@@ -511,10 +499,7 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
         for (int j = 0; j < Cfg::KG; ++j) {
             const float tot = rows_sum4_scatter(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
             const int idx   = 4 * j + frow;
-            if (idx < K && wr_lane) {
-                if constexpr (GSX_BWD_T_PRIVATE) s_acc[((int)wave * BATCH + t_g) * KP + idx] += tot; // this wave's own table
-                else atomicAdd(&s_acc[t_g * KP + idx], tot);                                        // ds_add_f32
-            }
+            if (idx < K && wr_lane) atomicAdd(&s_acc[t_g * KP + idx], tot); // ds_add_f32
         }
         if (frow == 0 && wr_lane) s_touch[t_g] = 1;
         wave_lds_sync();
@@ -632,15 +617,9 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
         for (int e = (int)tid; e < batch_size * NCOL; e += (int)blockDim.x) {
             const int s = e / NCOL, c = e - s * NCOL;
             if (!s_touch[s]) continue;
-            float rowv[KP];
+            float row[KP];
 #pragma unroll
-            for (int k = 0; k < KP; ++k) {
-                float v = s_acc[s * KP + k];
-#pragma unroll
-                for (int w = 1; w < Cfg::NACC; ++w) v += s_acc[(w * BATCH + s) * KP + k];
-                rowv[k] = v;
-            }
-            const float *row = rowv;
+            for (int k = 0; k < KP; ++k) row[k] = s_acc[s * KP + k];
             const float4 cu  = s_cull[s];
             const float ax = cu.x, ay = cu.y; // mean - tile centre: the moments are about the tile centre too
             const float S0 = row[CH], Su = row[CH + 1], Sv = row[CH + 2];
@@ -657,7 +636,7 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
             } else if (c == 4) {
                 val = 0.5f * (ay * (ay * S0 - 2.0f * Sv) + row[CH + 5]);
             } else if (c == 5) {
-                val = -S0 * __builtin_amdgcn_exp2f(kLoMargin - s_st[s].p0.w); // 1 / opacity
+                val = -S0 * __builtin_amdgcn_exp2f(-s_st[s].p0.w); // 1 / opacity
             } else {
                 const int k = c - 6;
                 if (k >= (int)a.nch) continue;
@@ -670,9 +649,7 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
         for (int s = (int)tid; s < BATCH; s += (int)blockDim.x) {
             if (s < batch_size && s_touch[s]) {
 #pragma unroll
-                for (int w = 0; w < Cfg::NACC; ++w)
-#pragma unroll
-                    for (int k = 0; k < KP; ++k) s_acc[(w * BATCH + s) * KP + k] = 0.0f;
+                for (int k = 0; k < KP; ++k) s_acc[s * KP + k] = 0.0f;
                 s_touch[s] = 0;
             }
         }
@@ -703,15 +680,6 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
 #ifndef GSX_BWD_W_ABS_WAVES
 #define GSX_BWD_W_ABS_WAVES 2
 #endif
-#ifndef GSX_BWD_W_PREFETCH // the next survivor's staged row is read while the current one is composited
-#define GSX_BWD_W_PREFETCH 0
-#endif
-#ifndef GSX_BWD_W_EAGER // exponent / alpha / validity of the four quadrants before any branch
-#define GSX_BWD_W_EAGER 0
-#endif
-#ifndef GSX_BWD_W_STAGE_AHEAD // the next batch's rows are requested before the current batch is walked
-#define GSX_BWD_W_STAGE_AHEAD 1
-#endif
 template <int CH, bool ABS = false>
 struct BwdWCfg {
     static constexpr int GEO   = 6 + (ABS ? 2 : 0); // geometry columns of the gradient row (+ |v_mean2d| with absgrad)
@@ -739,7 +707,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
     static_assert(CH <= 4, "cotangent rows are exchanged as float4");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    StagedRow *s_st = reinterpret_cast<StagedRow *>(smem_raw);  // e-form of the exponent + colours (raster3d.hpp)
+    StagedRow *s_st = reinterpret_cast<StagedRow *>(smem_raw);  // staged offset form of the exponent + colours (raster3d.hpp)
     float4 *s_aux   = reinterpret_cast<float4 *>(s_st + BATCH); // mean - tile centre (x, y), flatten id (bits), -
     float *s_w      = reinterpret_cast<float *>(s_aux + BATCH); // [SLOTS][4 quadrants][4 groups][GP]: (fac, w) per pixel
 
@@ -838,11 +806,8 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
             [[maybe_unused]] float gxr[2] = {0.f, 0.f}, gyr[2] = {0.f, 0.f}, ax2 = 0.f, bx1 = 0.f, sabs[2] = {0.f, 0.f};
             if constexpr (ABS) {
                 const v4f q0 = s_st[info >> 4].p0, q1 = s_st[info >> 4].p1; // staged row | nA, nB, nC, -
-#if GSX_DFORM // row = (ax, ay, lo, lo): the gradient of the exponent at the tile centre from the mean's offset
+                // row = (ax, ay, lo, lo): the gradient of the exponent at the tile centre from the mean's offset
                 const float gu = -fmaf(2.0f * q1.x, q0.x, q1.y * q0.y), gv = -fmaf(q1.y, q0.x, 2.0f * q1.z * q0.y);
-#else         // row = (e0, gu, gv, lo)
-                const float gu = q0.y, gv = q0.z;
-#endif
                 ax2 = 2.0f * q1.x; bx1 = q1.y;
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
@@ -896,7 +861,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
             const int t_g    = info >> 4;
             const float4 aux = s_aux[t_g];
             const v4f p1     = s_st[t_g].p1; // (-A, -B, -C) of the staged form: Q = (2A, B; B, 2C) / log2(e)
-            const float lo   = s_st[t_g].p0.w - kLoMargin;
+            const float lo   = s_st[t_g].p0.w;
             const float ax = aux.x, ay = aux.y;
             const int32_t id = __float_as_int(aux.z);
             const float S0 = acc[CH], Su = acc[CH + 1], Sv = acc[CH + 2];
@@ -926,7 +891,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
 
     // Staging is wave-private, so its two dependent global reads (list entry -> the Gaussian's rows) would sit in front of every
     // batch with nothing of this wave to hide them: the rows of batch b + 1 and the list entries of batch b + 2 are requested
-    // before batch b is walked (GSX_BWD_W_STAGE_AHEAD=0: the plain order, for A/B).
+    // before batch b is walked.
     struct Fetched { float2 xy; float opac, ca, cb, cc, cv[4]; };
     auto entry_of = [&](int32_t b) -> int32_t { // flatten id of this lane's entry of batch b, -1 = none
         const int32_t idx = range_end - 1 - BATCH * b - (int32_t)lane;
@@ -941,25 +906,17 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
 #pragma unroll
         for (int k = 0; k < 4; ++k) f.cv[k] = (k < CH && k < (int)a.nch) ? cp[k] : 0.0f;
     };
-#if GSX_BWD_W_STAGE_AHEAD
     int32_t g_cur = entry_of(0), g_nxt = entry_of(1);
     Fetched f_cur{};
     fetch(g_cur, f_cur);
-#endif
     for (int32_t b = 0; b < n_batches; ++b) {
         // back to front: staged slot s is list entry batch_end - s
         const int32_t batch_end = range_end - 1 - BATCH * b;
         int hitmask             = 0; // this lane's staged Gaussian: quadrants whose pixels it can reach
         {
             const int32_t idx = batch_end - (int32_t)lane;
-#if GSX_BWD_W_STAGE_AHEAD
             const int32_t g = g_cur;
             const Fetched f = f_cur;
-#else
-            const int32_t g = entry_of(b);
-            Fetched f{};
-            fetch(g, f);
-#endif
             if (g >= 0) {
                 const float opac = f.opac, ca = f.ca, cb = f.cb, cc = f.cc;
                 const float ax = f.xy.x - tile_cx, ay = f.xy.y - tile_cy;
@@ -984,36 +941,20 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
                 }
             }
         }
-#if GSX_BWD_W_STAGE_AHEAD
         g_cur = g_nxt;
         fetch(g_cur, f_cur);   // rows of batch b + 1: in flight while batch b is walked
         g_nxt = entry_of(b + 2);
-#endif
         wave_lds_sync();
 
         const int32_t behind_s = __builtin_amdgcn_readfirstlane(batch_end); // list index of staged slot t = behind_s - t
         uint64_t todo          = __builtin_amdgcn_ballot_w64(hitmask != 0);
-#if GSX_BWD_W_PREFETCH
-        // software pipeline: the staged row of the NEXT survivor is requested while the current one is composited
-        int32_t t_next = todo ? (int32_t)__builtin_ctzll(todo) : 0;
-        v4f n0 = s_st[t_next].p0, n1 = s_st[t_next].p1, n2 = s_st[t_next].p2;
-#endif
         while (todo) {
-#if GSX_BWD_W_PREFETCH
-            const int32_t t = t_next;
-            asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(t));
-            const v4f p0 = n0, p1 = n1, p2 = n2;
-            t_next = todo ? (int32_t)__builtin_ctzll(todo) : t;
-            n0 = s_st[t_next].p0; n1 = s_st[t_next].p1; n2 = s_st[t_next].p2;
-            const int qm = __builtin_amdgcn_readlane(hitmask, t);
-#else
             const int32_t t = (int32_t)__builtin_ctzll(todo);
             asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(t)); // todo &= todo - 1 in one scalar instruction
             const int qm = __builtin_amdgcn_readlane(hitmask, t);
             const v4f p0 = s_st[t].p0;
             const v4f p1 = s_st[t].p1;
             const v4f p2 = s_st[t].p2;
-#endif
             float col[CH];
             col[0] = p2.x;
             if constexpr (CH > 1) col[1] = p2.y;
@@ -1021,31 +962,14 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
             if constexpr (CH > 3) col[3] = p2.z;
             const int32_t list_idx = behind_s - t;
             int contributed        = 0; // wave-uniform
-#if GSX_BWD_W_EAGER
-            // the four quadrants' exponent / alpha / validity first, branch-free (four independent chains in flight), ...
-            float ov_q[4], al_q[4];
-            bool valid_q[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float e = staged_f(p0, p1.x, p1.y, p1.z, pu[q & 1], pv[q >> 1]);
-                ov_q[q]       = __builtin_amdgcn_exp2f(e);
-                al_q[q]       = fminf(kMaxAlpha, ov_q[q]);
-                valid_q[q]    = (qm & (1 << q)) && (bin_final[q] >= list_idx) && !(e > p0.w) && !(al_q[q] < kAlphaThreshold);
-            }
-#endif
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-#if GSX_BWD_W_EAGER
-                const float ov_r = ov_q[q], al_r = al_q[q];
-                const bool valid = valid_q[q];
-#else
                 if (!(qm & (1 << q))) continue; // scalar
                 const float e    = staged_f(p0, p1.x, p1.y, p1.z, pu[q & 1], pv[q >> 1]);
                 const float ov_r = __builtin_amdgcn_exp2f(e); // opac * exp(-sigma), unclamped
                 const float al_r = fminf(kMaxAlpha, ov_r);
                 // pixels outside the image have bin_final = -1 and can never be valid; e > lo <=> sigma < 0
                 const bool valid = (bin_final[q] >= list_idx) && !(e > p0.w) && !(al_r < kAlphaThreshold);
-#endif
                 if (__builtin_amdgcn_ballot_w64(valid) == 0ull) continue; // wave-uniform
                 // invalid lanes: alpha = 0 -> fac = 0, w = 0, T and `behind` unchanged (1 / (1 - 0) == 1 exactly)
                 const float alpha = valid ? al_r : 0.0f;
@@ -1106,35 +1030,37 @@ raster3d_bwd_w_abs_kernel(Raster3DArgs a)
     raster3d_bwd_w_body<CH, true>(a);
 }
 
-// GSX_RASTER3D_BWD=r|t|w selects the kernel for <= 4 channels per launch (default GSX_RASTER3D_BWD_DEFAULT; read once per process).
-static char bwd_variant()
+// The one place that decides which kernel takes a channel chunk (nch <= 32 channels of a call). GSX_RASTER3D_BWD=r|t|w (default
+// w; read once per process) names the kernel for <= 4 channels; r keeps the reduction kernel for wide rows too.
+BwdKernel raster3d_bwd_kernel(uint32_t tile_size, uint32_t nch, bool has_abs)
 {
     static const char v = [] {
         const char *e = getenv("GSX_RASTER3D_BWD");
         if (e && (e[0] == 'r' || e[0] == 'R')) return 'r';
         if (e && (e[0] == 't' || e[0] == 'T')) return 't';
-        if (e && (e[0] == 'w' || e[0] == 'W')) return 'w';
-        return GSX_RASTER3D_BWD_DEFAULT;
+        return 'w';
     }();
-    return v;
+    if (tile_size != 16 || v == 'r') return BwdKernel::R;
+    if (nch > 4) return !has_abs && nch <= 32 ? BwdKernel::M : BwdKernel::R; // 5 .. 32 channels: raster3d_bwd_m.hip
+    if (v == 'w') return BwdKernel::W;
+    return has_abs ? BwdKernel::R : BwdKernel::T;
 }
-static bool use_variant_t() { return bwd_variant() != 'r'; }
 
 template <int CH, bool ABS>
-static int launch_bwd(const Raster3DArgs &a, hipStream_t stream)
+static int launch_bwd(const Raster3DArgs &a, BwdKernel kernel, hipStream_t stream)
 {
     const uint32_t n_blocks = a.sp_active_tiles ? a.n_active : a.tile_w * a.tile_h * a.n_images;
     if (n_blocks == 0 || a.n_isects == 0) return GSX_OK;
     const uint32_t grid  = ((n_blocks + 7u) / 8u) * 8u;
     if constexpr (CH <= 4) {
-        if (a.tile_size == 16 && bwd_variant() == 'w') {
+        if (kernel == BwdKernel::W) {
             if constexpr (ABS) raster3d_bwd_w_abs_kernel<CH><<<dim3(grid), dim3(64), BwdWCfg<CH, true>::smem, stream>>>(a);
             else if constexpr (CH == 4) raster3d_bwd_w4_kernel<<<dim3(grid), dim3(64), BwdWCfg<4>::smem, stream>>>(a);
             else raster3d_bwd_w_kernel<CH><<<dim3(grid), dim3(64), BwdWCfg<CH>::smem, stream>>>(a);
             return check_launch("raster3d_bwd_w");
         }
         if constexpr (!ABS) {
-            if (a.tile_size == 16 && use_variant_t()) {
+            if (kernel == BwdKernel::T) {
                 raster3d_bwd_t_kernel<CH><<<dim3(grid), dim3(256), BwdTCfg<CH>::smem, stream>>>(a);
                 return check_launch("raster3d_bwd_t");
             }
@@ -1157,7 +1083,6 @@ int raster3d_bwd_t_launch_items(const Raster3DArgs &a, hipStream_t stream)
     });
     return check_launch("raster3d_bwd_t(segments)");
 }
-bool raster3d_bwd_uses_variant_t() { return use_variant_t(); }
 template <bool ABS>
 static int bwd_dispatch(Raster3DArgs a, hipStream_t stream)
 {
@@ -1169,9 +1094,9 @@ static int bwd_dispatch(Raster3DArgs a, hipStream_t stream)
         a.ch_off           = off;
         a.nch              = n;
         a.first_chunk      = first ? 1u : 0u;
-        int rc;
-        if (bwd_variant() != 'r' && raster3d_bwd_m_applies(a, ABS)) rc = raster3d_bwd_m_launch(a, stream); // 5 .. 32 channels: raster3d_bwd_m.hip
-        else rc = with_channels(n, [&](auto ch) { return launch_bwd<ch(), ABS>(a, stream); });
+        const BwdKernel kernel = raster3d_bwd_kernel(a.tile_size, n, ABS);
+        const int rc           = kernel == BwdKernel::M ? raster3d_bwd_m_launch(a, stream)
+                                                        : with_channels(n, [&](auto ch) { return launch_bwd<ch(), ABS>(a, kernel, stream); });
         if (rc != GSX_OK) return rc;
         off += n;
         first = false;
@@ -1247,10 +1172,8 @@ extern "C" int gsx_raster3d_bwd_fill(
         GSX_REQUIRE(v_colors_channel_stride >= 0, "gsx_raster3d_bwd_ws: negative channel stride");
         a.vrc_strided = 1u; a.vrc_ps = v_colors_pixel_stride; a.vrc_cs = v_colors_channel_stride;
     }
-    // the launches that read the order: variant W (also with absgrad), variant T, the matrix-core kernel
-    a.nch = cdim > 32 ? 32 : cdim; // what the first launch will see (bwd_dispatch sets it per chunk)
-    const bool wide_m = cdim > 4 && bwd_variant() != 'r' && raster3d_bwd_m_applies(a, has_abs != 0);
-    if (wide_m || (bwd_variant() == 'w' ? (tile_size == 16 && cdim <= 4) : (!has_abs && cdim <= 4 && bwd_variant() != 'r'))) {
+    // every kernel but the reduction kernel reads the order: built for the first chunk's kernel, later chunks reuse it
+    if (raster3d_bwd_kernel(tile_size, cdim > 32 ? 32 : cdim, has_abs != 0) != BwdKernel::R) {
         int rc       = GSX_OK;
         a.tile_order = fill.tile_order(a, workspace, workspace_bytes, &rc);
         if (rc != GSX_OK) return rc;

@@ -40,9 +40,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #ifndef GSX_BWD_M_WAVES
 #define GSX_BWD_M_WAVES 3
 #endif
-#ifndef GSX_BWD_M_DBG // timing ablations (A/B builds only; results are wrong when set): 1 no colour atomics, 2 no gradient
-#define GSX_BWD_M_DBG 0 // MFMAs, 4 no dot-product MFMAs, 8 no pixel walk, 16 no geometry flush, 32 no colour staging
-#endif
 #ifndef GSX_BWD_M_ILP // survivors whose state-independent half is formed together (see the walk)
 #define GSX_BWD_M_ILP 1
 #endif
@@ -74,7 +71,7 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
     constexpr int CP    = Cfg::CP;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    StagedRow *s_st  = reinterpret_cast<StagedRow *>(smem_raw);      // e-form of the exponent (raster3d.hpp); its colour fields are unused
+    StagedRow *s_st  = reinterpret_cast<StagedRow *>(smem_raw);      // staged offset form of the exponent (raster3d.hpp); its colour fields are unused
     float4 *s_cull   = reinterpret_cast<float4 *>(s_st + BATCH);     // mean - tile centre, half extents of alpha >= 1/255
     int32_t *s_id    = reinterpret_cast<int32_t *>(s_cull + BATCH);  // flatten id of the row
     int32_t *s_touch = s_id + BATCH;
@@ -216,7 +213,7 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
                 const float *c  = a.colors + (size_t)g * a.cdim + a.ch_off + Q * part;
                 float cv[Q];
 #pragma unroll
-                for (int k = 0; k < Q; ++k) cv[k] = (!(GSX_BWD_M_DBG & 32) && Q * part + k < (int)a.nch) ? c[k] : 0.0f;
+                for (int k = 0; k < Q; ++k) cv[k] = (Q * part + k < (int)a.nch) ? c[k] : 0.0f;
                 f32x4 *dst = reinterpret_cast<f32x4 *>(s_col + s * CP + Q * part);
 #pragma unroll
                 for (int h = 0; h < Q / 4; ++h) dst[h] = f32x4{cv[4 * h], cv[4 * h + 1], cv[4 * h + 2], cv[4 * h + 3]};
@@ -264,12 +261,10 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
                 f32x4 d[4];
 #pragma unroll
                 for (int pb = 0; pb < 4; ++pb) d[pb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if !(GSX_BWD_M_DBG & 4)
 #pragma unroll
                 for (int s = 0; s < KC; ++s)
 #pragma unroll
                     for (int pb = 0; pb < 4; ++pb) d[pb] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[s], bdot[pb][s], d[pb], 0, 0, 0);
-#endif
                 // result (slot 4 bk + i, pixel 16 pb + bj) -> the cell the pixel's lane reads in (3) and overwrites with fac
 #pragma unroll
                 for (int pb = 0; pb < 4; ++pb)
@@ -284,7 +279,7 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
             // the wave takes parks zeros (its rows of the products are zero; `dead` keeps it out of the atomics).
             uint32_t dead = 0; // wave-uniform: slots no pixel of this wave took
             struct Front { float ov_r, al_r, cv; bool valid; };
-            for (int k0 = 0; k0 < ((GSX_BWD_M_DBG & 8) ? 0 : n); k0 += GSX_BWD_M_ILP) {
+            for (int k0 = 0; k0 < n; k0 += GSX_BWD_M_ILP) {
                 Front fr[GSX_BWD_M_ILP];
 #pragma unroll
                 for (int i = 0; i < GSX_BWD_M_ILP; ++i) {
@@ -335,14 +330,12 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
                 f32x4 acc_c[NB], acc_m = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) acc_c[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if !(GSX_BWD_M_DBG & 2)
 #pragma unroll
                 for (int s = 0; s < 16; ++s) {
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) acc_c[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], bcol[nb][s], acc_c[nb], 0, 0, 0);
                     acc_m = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[s], bphi[s], acc_m, 0, 0, 0);
                 }
-#endif
                 // results: column bj, rows 4 bk + i (C/D map of the 16x16 forms: col = lane & 15, row = 4 (lane >> 4) + i)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -353,11 +346,7 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
 #pragma unroll
                         for (int nb = 0; nb < NB; ++nb) {
                             const int ch = 16 * nb + bj;
-#if !(GSX_BWD_M_DBG & 1)
                             if (ch < (int)a.nch) atomic_add_f32(grow + ch, acc_c[nb][i]);
-#else
-                            if (ch < (int)a.nch && acc_c[nb][i] == 1234.5f) atomic_add_f32(grow + ch, acc_c[nb][i]);
-#endif
                         }
                         if (bj < 6) atomicAdd(&s_acc[t_g * KA + bj], acc_m[i]); // ds_add_f32: six lanes per Gaussian
                         if (bj == 6) s_touch[t_g] = 1;
@@ -374,7 +363,7 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
         // floats of one row in HBM, and because a row's readers sit in ONE wave they can zero it themselves right after (LDS
         // operations of a wave execute in order) - no barrier between the flush and the re-zeroing, no separate zero pass.
         constexpr float kInvLog2e = 1.0f / kLog2e;
-        for (int e = (int)tid; e < ((GSX_BWD_M_DBG & 16) ? 0 : BATCH * KA); e += (int)blockDim.x) {
+        for (int e = (int)tid; e < BATCH * KA; e += (int)blockDim.x) {
             const int s = e >> 3, c = e & 7;
             const bool live = s < batch_size && s_touch[s] != 0; // the same for the eight lanes of a row
             float val = 0.0f;
@@ -394,7 +383,7 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
                 } else if (c == 4) {
                     val = 0.5f * (ay * (ay * S0 - 2.0f * Sv) + row[5]);
                 } else {
-                    val = -S0 * __builtin_amdgcn_exp2f(kLoMargin - s_st[s].p0.w); // v_opacity = sum vis v_alpha = -S_w / opacity
+                    val = -S0 * __builtin_amdgcn_exp2f(-s_st[s].p0.w); // v_opacity = sum vis v_alpha = -S_w / opacity
                 }
                 atomic_add_f32(a.v_rows + (size_t)s_id[s] * a.row_stride + c, val);
             }
@@ -410,19 +399,6 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
     }
 }
 
-// GSX_RASTER3D_BWD_WIDE=r keeps the reduction kernel for wide colour rows (A/B; read once per process)
-static bool bwd_m_enabled()
-{
-    static const bool on = [] {
-        const char *e = getenv("GSX_RASTER3D_BWD_WIDE");
-        return !(e && (e[0] == 'r' || e[0] == 'R' || e[0] == '0'));
-    }();
-    return on;
-}
-bool raster3d_bwd_m_applies(const Raster3DArgs &a, bool has_abs)
-{
-    return bwd_m_enabled() && !has_abs && a.tile_size == 16 && a.nch > 4 && a.nch <= 32;
-}
 int raster3d_bwd_m_launch(const Raster3DArgs &a, hipStream_t stream)
 {
     const uint32_t n_blocks = a.sp_active_tiles ? a.n_active : a.tile_w * a.tile_h * a.n_images;

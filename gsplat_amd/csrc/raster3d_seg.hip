@@ -31,7 +31,6 @@ namespace gsx {
 int raster3d_fwd_launch_chunk(const Raster3DArgs &a, hipStream_t stream);   // raster3d_fwd.hip
 int raster3d_bwd_prepass_launch(const Raster3DArgs &a, hipStream_t stream); // raster3d_fwd.hip (forward kernel, PRE = true)
 int raster3d_bwd_t_launch_items(const Raster3DArgs &a, hipStream_t stream); // raster3d_bwd.hip
-bool raster3d_bwd_uses_variant_t();
 
 struct SegHeader { // device memory, zeroed before every use
     int32_t n_items, n_long, pad[2];
@@ -354,7 +353,7 @@ static int raster3d_bwd_seg_impl(
     GSX_REQUIRE(tile_size == 16 && cdim >= 1 && cdim <= 4,
                 "gsx_raster3d_bwd_seg: needs 16 x 16 tiles and <= 4 channels (got tile %u, %u channels): use gsx_raster3d_bwd",
                 tile_size, cdim);
-    if (!raster3d_bwd_uses_variant_t()) // GSX_RASTER3D_BWD=r (A/B switch): the reduction kernel has no segment support
+    if (raster3d_bwd_kernel(tile_size, cdim, false) == BwdKernel::R) // GSX_RASTER3D_BWD=r: the reduction kernel has no segment support
         return gsx_raster3d_bwd(means2d, conics, colors, opacities, backgrounds, masks, isect_offsets, flatten_ids, render_alphas,
                                 last_ids, v_render_colors, v_render_alphas, n_images, n_isects, cdim, width, height, tile_size,
                                 tile_w, tile_h, 0, v_rows, row_stride, stream);

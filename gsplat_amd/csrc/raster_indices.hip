@@ -7,12 +7,11 @@
 // `range_start` / `range_end` count batches of tile_size^2 list entries, as in the reference. Not a hot path: one thread
 // per pixel, parameters read straight from global memory.
 //
-// The alpha of a pair is evaluated with the SAME staged forms as the compositing kernels (raster3d.hpp: stage_gaussian_e /
-// staged_e about the tile centre; raster2d.hpp: stage_surfel / eval_surfel) and the transmittance advances with the same
-// fma, so that the set of pairs this op reports IS the set the rasterizer blends - the contract of the reference, whose
-// two kernels share one device function (RasterizeToPixels3DGSDevice.cuh). The reference's own PyTorch rasterizer
-// (_torch_impl.py:_rasterize_to_pixels) takes its pairs from this op and is compared with the rasterizer at 1e-5: an
-// alpha test decided by two different roundings flips a pair per ~10^5 pixels (reference suite, round 6).
+// The alpha of a pair is evaluated with the SAME staged forms as the compositing kernels (raster3d.hpp: stage_gaussian_f /
+// staged_f; raster2d.hpp: stage_surfel / eval_surfel) and the transmittance advances with the same fma: the set of pairs
+// this op reports IS the set the rasterizer blends - the contract of the reference, whose two kernels share one device function
+// (RasterizeToPixels3DGSDevice.cuh). Its PyTorch rasterizer (_torch_impl.py:_rasterize_to_pixels) takes its pairs from this op
+// and is compared with the rasterizer at 1e-5: an alpha test decided by two roundings flips a pair per ~10^5 pixels.
 #include "raster2d.hpp"
 
 namespace gsx {
@@ -63,7 +62,7 @@ __global__ void __launch_bounds__(256) raster_indices_kernel(const IndicesArgs a
             stage_gaussian_f(mx - tcx, my - tcy, a.opacities[g], c[0], c[1], c[2], p0, nA, nB, nC);
             const float e = staged_f(p0, nA, nB, nC, u, v);
             alpha = fminf(kMaxAlpha, __builtin_amdgcn_exp2f(e));
-            valid = !(e > p0.w) && !(alpha < kAlphaThreshold); // e > lo (+ margin) <=> sigma < 0
+            valid = !(e > p0.w) && !(alpha < kAlphaThreshold); // e > lo <=> sigma < 0
         } else {
             float4 A, B, C;
             stage_surfel(a.geom + 9 * (size_t)g, mx, my, a.opacities[g], tcx, tcy, A, B, C);

@@ -207,3 +207,27 @@ def test_longest_list_notes_are_keyed_by_tensor_identity_and_expired_slots_go_fi
     note(extra, 999)  # 17 live tensors: the oldest note goes
     assert lookup(extra) == 999 and lookup(live[0]) == 0
     assert [lookup(t) for t in live[1:]] == [101 + i for i in range(15)]
+
+
+def test_environment_switches_read_by_the_library_are_the_documented_ones():
+    """Text only: every GSX_* / GSPLAT_AMD_* name the native sources pass to getenv appears in INTEGRATION.md, and every GSX_*
+    name of its "Switches for A/B runs and tests" paragraph is read by a getenv somewhere under gsplat_amd/csrc."""
+    import re
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "gsplat_amd", "csrc")
+    read = set()
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".hpp", ".cpp", ".h")):
+            with open(os.path.join(csrc, name)) as f:
+                read |= set(re.findall(r'getenv\(\s*"((?:GSX|GSPLAT_AMD)_[A-Z0-9_]+)"', f.read()))
+    assert len(read) >= 8, read  # the pattern still finds the calls
+    with open(os.path.join(root, "INTEGRATION.md")) as f:
+        doc = f.read()
+    documented = set(re.findall(r"\b(?:GSX|GSPLAT_AMD)_[A-Z0-9_]+", doc))
+    assert read <= documented, f"read by the library, missing from INTEGRATION.md: {sorted(read - documented)}"
+    start = doc.index("**Switches for A/B runs and tests**")
+    paragraph = doc[start:doc.index("\n\n", start)]
+    listed = set(re.findall(r"\bGSX_[A-Z0-9_]+", paragraph))
+    assert len(listed) >= 6, listed
+    assert listed <= read, f"listed as switches in INTEGRATION.md, read by nothing: {sorted(listed - read)}"

@@ -3,7 +3,7 @@
 test-suite pins bit for bit against the C oracle): every output must be IDENTICAL - tiles_per_gauss, isect_ids, flatten_ids,
 offsets - on scenes chosen to hit every branch (ellipse / box test, tile sizes, several images, packed rows, depth ties,
 giant Gaussians = oversized tiles and the workspace-overflow retry, sparse tile masks). Then times both on c3 / c4 for the
-bin shapes and LDS capacities the library can be switched to (GSX_ISECT_BIN, GSX_ISECT_CAP).
+bin shapes the library can be switched to (GSX_ISECT_BIN).
 usage: gpu_isect_check.py [check] [bench] [c4]"""
 import json, math, os, sys, time
 import torch
@@ -149,7 +149,7 @@ def bench_all(c4):
 
 
 def bench_one(c4):
-    """The auto path only (for rocprofv3 per-kernel traces and the GSX_ISECT_DBG ablations) + the list-length distribution."""
+    """The auto path only (for rocprofv3 per-kernel traces) + the list-length distribution."""
     sc, W, H = bench.make_workload(4_000_000 if c4 else 1_000_000, dev, n_cameras=4 if c4 else 1)
     rad, m2, d, con, op = project(sc, W, H)
     C = sc["viewmats"].shape[0]
@@ -165,7 +165,7 @@ def bench_one(c4):
     t = tpg.flatten()[tpg.flatten() > 0].float()
     rec["tiles_per_row"] = {"mean": round(float(t.mean()), 2), "p50": q(t, 0.5), "p90": q(t, 0.9), "p99": q(t, 0.99), "max": int(t.max()),
                             "rows": int(t.numel())}
-    print(json.dumps({"scene": "c4" if c4 else "c3", "dbg": os.environ.get("GSX_ISECT_DBG", "0"), **rec}), flush=True)
+    print(json.dumps({"scene": "c4" if c4 else "c3", **rec}), flush=True)
 
 
 if __name__ == "__main__":
