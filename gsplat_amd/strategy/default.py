@@ -12,6 +12,7 @@ test of the reference runs AFTER growth, on the children too; since a child's op
 parent's, the same test is evaluated on the plan before anything is materialised."""
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Any, Dict, Tuple, Union
 
@@ -19,12 +20,10 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 
-import os
-
-_FUSED_ACCUMULATE = os.environ.get("GSPLAT_AMD_STRATEGY_FUSED", "1") not in ("0", "")  # A/B: 0 = the tensor-op form
-
 from .base import Strategy
 from .ops import RowPlan, _quat_to_rotmat, apply_plan, reset_opa
+
+_FUSED_ACCUMULATE = os.environ.get("GSPLAT_AMD_STRATEGY_FUSED", "1") not in ("0", "")  # A/B: 0 = the tensor-op form
 
 Params = Union[Dict[str, torch.nn.Parameter], torch.nn.ParameterDict]
 
@@ -140,16 +139,20 @@ class DefaultStrategy(Strategy):
             return False
         radii = info["radii"]
         track = self.refine_scale2d_stop_iter > 0
+        # the kernel indexes every state tensor with the Gaussian's row (N elements, on the gradient's device) and reads a radii
+        # pair as one int2 (8-byte aligned); anything else takes the tensor-op form
         if not (grad.is_cuda and grad.dtype == torch.float32 and radii.dtype == torch.int32 and radii.is_contiguous()
+                and radii.device == grad.device and radii.data_ptr() % 8 == 0
                 and n > 0 and radii.numel() == grad.numel() and grad.numel() % (2 * n) == 0 and grad.shape[-1] == 2
-                and all(state[k].dtype == torch.float32 and state[k].is_contiguous() and state[k].is_cuda
+                and all(state[k].dtype == torch.float32 and state[k].is_contiguous() and state[k].device == grad.device
+                        and state[k].numel() == n
                         for k in ("grad2d", "count") + (("radii",) if track else ()))):
             return False
         rows = grad.reshape(-1, 2) if grad.is_contiguous() else None
         stride = 2
         if rows is None:  # [.., N, 2] view with one row stride throughout (a column pair of an array-of-structures buffer)
             st, shp = grad.stride(), grad.shape
-            if st[-1] != 1:
+            if st[-1] != 1 or st[-2] < 2:  # rows closer than two floats overlap: gsx_strategy_accumulate refuses them
                 return False
             stride, expect = st[-2], st[-2]
             for d in range(grad.dim() - 2, -1, -1):

@@ -43,6 +43,7 @@ def test_adam_matches_oracle(G, O, shape, masked):
     torch.testing.assert_close(vd.cpu(), ve, rtol=2e-5, atol=5e-7)  # fma contraction on the device
     if masked:  # masked rows are bit-identical to the inputs
         assert torch.equal(pd.cpu()[~valid], p[~valid]) and torch.equal(md.cpu()[~valid], m[~valid])
+        assert torch.equal(vd.cpu()[~valid], v[~valid])
 
 
 def test_selective_adam_optimizer(G, O):
