@@ -34,6 +34,10 @@ _LAZY = {
     "photometric_loss": "losses", "masked_l1": "losses", "masked_ssim": "losses", "mse_loss": "losses", "losses": "losses",
     # the per-image appearance correction between the render and the loss (examples/lib_bilagrid.py)
     "BilateralGrid": "bilagrid", "bilagrid": "bilagrid", "total_variation_loss": "losses",
+    # depth supervision (gsplat/losses.py:209-320; the trainers' depth_loss=True block)
+    "depth_l1_loss": "losses", "binocular_disparity_l1": "losses", "pearson_depth_loss": "losses",
+    "sampled_depth_l1_loss": "losses", "depth_l1_loss_torch": "losses", "binocular_disparity_l1_torch": "losses",
+    "pearson_depth_loss_torch": "losses", "sampled_depth_l1_loss_torch": "losses",
     # the per-Gaussian appearance MLP of the trainer's app_opt path (examples/utils.py: AppearanceOptModule)
     "AppearanceOptModule": "appearance", "appearance": "appearance",
     # before step 0: the nearest-neighbour scale initialisation (gsplat/init_utils.py, examples/utils.py: knn)

@@ -1165,6 +1165,60 @@ int gsx_plas_blur(const float *grid, int64_t H, int64_t W, uint32_t C, int64_t r
 int gsx_plas_step(float *grid, const float *target, int32_t *index, int64_t H, int64_t W, uint32_t C, uint32_t b, uint32_t seed,
                   uint32_t t, float *partials, float *result, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depth-supervision losses of the training step (gsplat/losses.py:209-320: depth_l1_loss, binocular_disparity_l1,
+ * pearson_depth_loss; examples/simple_trainer.py:962-980: the expected-depth render sampled at the SfM points). One pass over
+ * the inputs per direction and a one-workgroup finish; nothing is read back by the host - what the reference decides there
+ * (fewer than two samples, nothing selected, the clamp of the Pearson denominator) the finish kernel decides on the device.
+ * pred / gt: [d0, d1, d2, d3] float32 through element strides, 0 < d0 d1 d2 d3 < 2^31 (a [..., 3:4] view of a [C, H, W, 4]
+ * render is read in place). mask: NULL or a tensor addressed through its OWN element strides (0 along a broadcast dimension),
+ * elements GSX_MASK_F32 or GSX_MASK_U8; an element counts where mask != 0, and pred / gt are not read where it is 0.
+ *   Pearson     loss = 1 - Spg / sqrt(max(Spp Sgg, 1e-12)) over the n selected elements, 0 with zero gradient when n < 2;
+ *               record = (loss, n, mean_p, mean_g, Spp, Sgg, Spg, denominator). The clamp passes its gradient where
+ *               Spp Sgg >= 1e-12 and blocks it otherwise, as torch's does.
+ *   disparity   mode GSX_DEPTH_L1: loss = scale * mean over ALL elements of |disp(pred) - disp(gt)|, disp(x) = x > 0 ? 1 / x : 0
+ *               (mask must be NULL, eps is ignored). Mode GSX_DEPTH_BINOCULAR: loss = mean of |1 / pred - 1 / gt| over the pairs
+ *               with |pred| > eps, |gt| > eps and mask != 0, 0 when none counts (scale is ignored).
+ *               record = (loss, count, sum of |d|, gradient scale). v_pred = sign(d) (-1 / pred^2) scale / count on counted
+ *               elements with pred > 0 (L1) resp. counted pairs (binocular) and exactly 0 elsewhere: where pred <= 0 the L1
+ *               mode's gradient is 0, not the reference's NaN (inf * 0 in the backward of torch.where).
+ *   sampled     depth_map [C, H, W] through element strides (c, h, w), points [C, M, 2] = pixel coordinates (x, y) and depths_gt
+ *               [C, M] contiguous; the map is sampled bilinearly (F.grid_sample, align_corners=True, zeros outside the image) and
+ *               the samples go through the GSX_DEPTH_L1 loss. C H W < 2^31, C M < 2^31, H, W < 2^24. record as for disparity.
+ *               bwd: v_map [C, H, W] contiguous is zero-filled, then every point adds its four weighted taps with hardware float
+ *               atomics (points may share a pixel): bit-equal between runs when no two points share a tap, a few ulp otherwise.
+ *               No gradient at taps outside the image or where the sample is <= 0.
+ * fwd: partial_sums [GSX_DEPTH_PARTIALS * gsx_depth_blocks(element or point count)] doubles of scratch: per-workgroup sums
+ * (Pearson: centred moments, merged pairwise), combined by one workgroup in a fixed order in double (no float atomics: a loss
+ * repeats bit for bit). loss [1] float32 and record
+ * [GSX_DEPTH_RECORD] doubles stay in device memory.
+ * bwd: v_pred [d0, d1, d2, d3] contiguous, every element written = *grad_device * d loss / d pred, with record the forward's. */
+#define GSX_DEPTH_L1 0
+#define GSX_DEPTH_BINOCULAR 1
+#define GSX_DEPTH_PARTIALS 6
+#define GSX_DEPTH_RECORD 8
+int64_t gsx_depth_blocks(int64_t n);
+int gsx_depth_pearson_fwd(const float *pred, const int64_t *strides_pred, const float *gt, const int64_t *strides_gt,
+                          const void *mask, const int64_t *strides_mask, int mask_dtype, uint32_t d0, uint32_t d1, uint32_t d2,
+                          uint32_t d3, double *partial_sums, float *loss, double *record, void *stream);
+int gsx_depth_pearson_bwd(const float *pred, const int64_t *strides_pred, const float *gt, const int64_t *strides_gt,
+                          const void *mask, const int64_t *strides_mask, int mask_dtype, uint32_t d0, uint32_t d1, uint32_t d2,
+                          uint32_t d3, const double *record, const float *grad_device, float *v_pred, void *stream);
+int gsx_depth_disparity_fwd(const float *pred, const int64_t *strides_pred, const float *gt, const int64_t *strides_gt,
+                            const void *mask, const int64_t *strides_mask, int mask_dtype, uint32_t d0, uint32_t d1, uint32_t d2,
+                            uint32_t d3, int mode, float scale, float eps, double *partial_sums, float *loss, double *record,
+                            void *stream);
+int gsx_depth_disparity_bwd(const float *pred, const int64_t *strides_pred, const float *gt, const int64_t *strides_gt,
+                            const void *mask, const int64_t *strides_mask, int mask_dtype, uint32_t d0, uint32_t d1, uint32_t d2,
+                            uint32_t d3, int mode, float eps, const double *record, const float *grad_device, float *v_pred,
+                            void *stream);
+int gsx_depth_sampled_fwd(const float *depth_map, const int64_t *strides_map, uint32_t C, uint32_t H, uint32_t W,
+                          const float *points, const float *depths_gt, uint32_t M, float scale, double *partial_sums, float *loss,
+                          double *record, void *stream);
+int gsx_depth_sampled_bwd(const float *depth_map, const int64_t *strides_map, uint32_t C, uint32_t H, uint32_t W,
+                          const float *points, const float *depths_gt, uint32_t M, const double *record, const float *grad_device,
+                          float *v_map, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
