@@ -38,6 +38,8 @@ _LAZY = {
     "depth_l1_loss": "losses", "binocular_disparity_l1": "losses", "pearson_depth_loss": "losses",
     "sampled_depth_l1_loss": "losses", "depth_l1_loss_torch": "losses", "binocular_disparity_l1_torch": "losses",
     "pearson_depth_loss_torch": "losses", "sampled_depth_l1_loss_torch": "losses",
+    # colour correction before the appearance models are scored (gsplat/color_correct.py; the trainer's cc_psnr / cc_ssim / cc_lpips)
+    "color_correct_affine": "color_correct", "color_correct_quadratic": "color_correct", "color_correct": "color_correct",
     # the per-Gaussian appearance MLP of the trainer's app_opt path (examples/utils.py: AppearanceOptModule)
     "AppearanceOptModule": "appearance", "appearance": "appearance",
     # before step 0: the nearest-neighbour scale initialisation (gsplat/init_utils.py, examples/utils.py: knn)

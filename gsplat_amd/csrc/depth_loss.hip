@@ -29,7 +29,7 @@
 // Atomics: only gsx_depth_sampled_bwd uses them. It zero-fills the dense [C, H, W] gradient and adds each point's four weighted
 // taps with hardware float atomics (two SfM points may share a pixel), so that gradient is a float atomic sum: bit-equal between
 // runs when no two points share a tap, equal to a few ulp otherwise.
-#include "common.hpp"
+#include "moments.hpp"
 
 #include <math.h>
 
@@ -37,7 +37,7 @@ namespace gsx {
 
 constexpr int kDpThreads = 256, kDpPerThread = 4, kDpMaxBlocks = 1024;
 constexpr int kDpRecord = GSX_DEPTH_RECORD;
-static_assert(GSX_DEPTH_PARTIALS == 6, "the Pearson pass leaves six sums per workgroup");
+static_assert(GSX_DEPTH_PARTIALS == kMomentQuantities, "the Pearson pass leaves six sums per workgroup");
 constexpr int kDpPearson = -1; // the backward kernel's third mode, next to GSX_DEPTH_L1 / GSX_DEPTH_BINOCULAR
 
 struct DpArgs {
@@ -123,66 +123,18 @@ __global__ void __launch_bounds__(kDpThreads) depth_partial_kernel(const DpArgs 
     dp_block_sums<2>(acc, partial);
 }
 
-// centred moments of a set of (p, g) pairs
-struct Moments { double n, mp, mg, spp, sgg, spg; };
-
-// a and b merged, in this order (the rounding depends on it: every caller merges in a fixed order)
-__device__ __forceinline__ Moments mom_merge(const Moments &a, const Moments &b)
-{
-    if (b.n == 0.0) return a;
-    if (a.n == 0.0) return b;
-    const double n = a.n + b.n, dp = b.mp - a.mp, dg = b.mg - a.mg, w = a.n * b.n / n, f = b.n / n;
-    return {n, a.mp + dp * f, a.mg + dg * f, a.spp + b.spp + dp * dp * w, a.sgg + b.sgg + dg * dg * w, a.spg + b.spg + dp * dg * w};
-}
-
-__device__ __forceinline__ Moments mom_shfl_down(const Moments &m, int o)
-{
-    return {__shfl_down(m.n, o), __shfl_down(m.mp, o), __shfl_down(m.mg, o), __shfl_down(m.spp, o), __shfl_down(m.sgg, o),
-            __shfl_down(m.spg, o)};
-}
-
-__device__ __forceinline__ void mom_store(double *dst, int64_t stride, const Moments &m)
-{
-    dst[0] = m.n; dst[stride] = m.mp; dst[2 * stride] = m.mg; dst[3 * stride] = m.spp; dst[4 * stride] = m.sgg; dst[5 * stride] = m.spg;
-}
-
-__device__ __forceinline__ Moments mom_load(const double *src, int64_t stride)
-{
-    return {src[0], src[stride], src[2 * stride], src[3 * stride], src[4 * stride], src[5 * stride]};
-}
-
-// the moments of all threads of the workgroup, valid in thread 0: lanes by a shuffle tree, then the waves in order
-__device__ __forceinline__ Moments mom_block(Moments m, double *s_red)
-{
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) m = mom_merge(m, mom_shfl_down(m, o)); // lane 0: ((0, 1), (2, 3)), ...
-    if (lane_id() == 0) mom_store(s_red + threadIdx.x / kWave, kDpThreads / kWave, m);
-    __syncthreads();
-    Moments t{};
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kDpThreads / kWave; ++w) t = mom_merge(t, mom_load(s_red + w, kDpThreads / kWave));
-    return t;
-}
-
 template <bool LINEAR>
 __global__ void __launch_bounds__(kDpThreads) depth_pearson_partial_kernel(const DpArgs a, double *partial)
 {
     __shared__ double s_red[GSX_DEPTH_PARTIALS * kDpThreads / kWave];
-    double n = 0.0, qp = 0.0, qg = 0.0, sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
+    MomentSums sums; // about the thread's pivot: its first selected pair
     for (uint64_t e = (uint64_t)blockIdx.x * kDpThreads + threadIdx.x; e < a.n; e += (uint64_t)gridDim.x * kDpThreads) {
         const DpOffsets o = dp_offsets<LINEAR>(a, (uint32_t)e);
         if (!dp_selected(a, o.m)) continue; // an element the mask drops is not read
-        const double p = (double)a.pred[o.p], g = (double)a.gt[o.g];
-        if (n == 0.0) { qp = p; qg = g; } // the thread's pivot: its first selected pair
-        const double x = p - qp, y = g - qg;
-        n += 1.0; sx += x; sy += y; sxx += x * x; syy += y * y; sxy += x * y;
+        sums.add((double)a.pred[o.p], (double)a.gt[o.g]);
     }
-    Moments m{};
-    if (n > 0.0) {
-        const double mx = sx / n, my = sy / n;
-        m = {n, qp + mx, qg + my, sxx - sx * mx, syy - sy * my, sxy - sx * my};
-    }
-    m = mom_block(m, s_red);
+    Moments m = sums.moments();
+    m = mom_block<kDpThreads>(m, s_red);
     if (threadIdx.x == 0) mom_store(partial + blockIdx.x, gridDim.x, m);
 }
 
@@ -194,7 +146,7 @@ __global__ void __launch_bounds__(kDpThreads) depth_pearson_finish_kernel(const 
     __shared__ double s_red[GSX_DEPTH_PARTIALS * kDpThreads / kWave];
     Moments m{};
     for (int i = threadIdx.x; i < n_blocks; i += kDpThreads) m = mom_merge(m, mom_load(partial + i, n_blocks));
-    m = mom_block(m, s_red);
+    m = mom_block<kDpThreads>(m, s_red);
     if (threadIdx.x != 0) return;
     double r[kDpRecord] = {};
     r[1] = m.n;

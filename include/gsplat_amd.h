@@ -1219,6 +1219,31 @@ int gsx_depth_sampled_bwd(const float *depth_map, const int64_t *strides_map, ui
                           const float *points, const float *depths_gt, uint32_t M, const double *record, const float *grad_device,
                           float *v_map, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Colour correction of a render against its ground truth before it is scored (gsplat/color_correct.py: color_correct_quadratic,
+ * color_correct_affine; the trainer's use_color_correction_metric block). img, ref and out: [n, 3] float32, contiguous,
+ * 0 < 3 n < 2^31; all n pixels form one set and one warp serves the whole call. No gradients.
+ *   quadratic   num_iters in [1, GSX_CC_MAX_ITERS] rounds. Round k reads img and ref, re-applies the warps W_0 .. W_{k-1} in
+ *               registers and sums, per channel c and in double, the 10 x 10 normal equations of the fit of ref_c by the features
+ *               (rr, rg, rb, gg, gb, bb, r, g, b, 1) of the current pixel over the rows where the original img_c, the current
+ *               img_c and ref_c all lie in [float32(eps), float32(1 - eps)] (both ends included; 1 - eps formed in double). One
+ *               workgroup adds the workgroups' sums in a fixed order, scales each Gram matrix to unit diagonal and solves it by
+ *               Cholesky in double: warps [num_iters, 10, 3] doubles, W_k[:, c] the solution of channel c. A warp is evaluated
+ *               in double, clipped to [0, 1] and rounded to float32 once. A last pass applies all warps to img and writes out:
+ *               2 num_iters + 1 launches. status [1]: cleared by the call; bit c is set when a system of channel c had a zero
+ *               diagonal entry or a scaled pivot <= 1e-10 (rank-deficient: a grey image, a channel without usable rows, fewer
+ *               than ten distinct pixels); that warp column is left zero and out is not meaningful. The caller reads status.
+ *   affine      per channel a = Cov(ref, img) / max(Var(ref), 1e-8), b = mean(img) - a mean(ref) from centred moments in double
+ *               (merged pairwise in a fixed order), a = 1 where |a| < 1e-8; out = clip((img - b) / a, 0, 1) evaluated in double.
+ *               coef [3, 2] doubles = (a, b) per channel.
+ * partial_sums [GSX_CC_PARTIALS * gsx_cc_blocks(n)] doubles of scratch for either. No float atomics: out repeats bit for bit. */
+#define GSX_CC_PARTIALS 195
+#define GSX_CC_MAX_ITERS 64
+int64_t gsx_cc_blocks(int64_t n);
+int gsx_cc_quadratic(const float *img, const float *ref, int64_t n, int num_iters, double eps, double *partial_sums,
+                     double *warps, uint32_t *status, float *out, void *stream);
+int gsx_cc_affine(const float *img, const float *ref, int64_t n, double *partial_sums, double *coef, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
