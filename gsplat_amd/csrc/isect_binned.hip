@@ -24,7 +24,8 @@
 //   G  bin_sort      one workgroup per bin: every entry is dealt to the LDS lists of the tiles in its mask (LDS cursors:
 //                    integer LDS atomics run at the rate of LDS writes on gfx950), then ONE WAVE PER TILE sorts its list
 //                    with a bitonic network that needs no workgroup barrier and writes keys (image|tile|depth) and row ids
-//                    contiguously. Tiles that do not fit the LDS arena together go in further batches; a tile longer than
+//                    contiguously (a list just over a power of two as two runs merged on the way out: bn_sort_list).
+//                    Tiles that do not fit the LDS arena together go in further batches; a tile longer than
 //                    the arena goes through the work-list sort of tile_sort.hip (launch_big_tile_sort).
 //
 // Measured on MI355X (tools/issue_rate.hip): ONE wave issues an instruction every ~5 cycles whatever the dependencies, a SIMD
@@ -574,9 +575,130 @@ __global__ void __launch_bounds__(1024) tile_plan_kernel(const BinArgs a)
 // ---- G: per bin: deal the entries to the tiles' LDS lists, one wave sorts each list, write ---------------------------------
 // The network is bitonic64.hpp's: on the keys as doubles (v_min_f64 / v_max_f64) unless a list holds a depth that does not
 // order like a positive normal double (the deal loop flags it) - that list takes the integer network.
-constexpr int kArenaPerWave = 512; // arena sort words per tile-wave: 16 waves -> 8192 words (+ 1/8 padding) = 72 KiB
+//
+// A list just over a power of two does not pay for the next one (profiles/r13_split_lists.md): H < n <= H + H / 4 entries with
+// H >= 256 take H + round_up(n - H, 8) words of the arena and are sorted as TWO RUNS - the first H dealt entries and the tail -,
+// which are merged on the way out: an element goes to its index in its run + its rank in the other run (bn_sort_split).
+constexpr int kArenaPerWave = 544; // arena sort words per tile-wave: 8 waves -> 4352 words (+ 1/8 padding) = 38.25 KiB, four
+                                   // workgroups per CU; 512 + the 8 % that lets a bin of c3 (lists of 466 +- 29) sort in one batch
 
-__global__ void __launch_bounds__(1024) bin_sort_kernel(const BinArgs a)
+// arena words the list of n entries sorts in; head = H when the list is split into runs of H and n - H, else 0
+__host__ __device__ __forceinline__ int bn_list_words(int n, int &head)
+{
+    head = 0;
+    if (n <= 0) return 0;
+    int P = 64;
+    while (P < n) P <<= 1;
+    const int H = P >> 1;
+    if (H >= 256 && n - H <= (H >> 2)) {
+        head = H;
+        return H + ((n - H + 7) & ~7);
+    }
+    return P;
+}
+
+// rank of each of four words among the sorted run s[first .. first + len) (logical indices, len >= 1): how many of the run's
+// words are smaller as unsigned integers. len is wave-uniform, so the four searches take their steps together.
+__device__ __forceinline__ void bn_rank4(const uint64_t *s, int first, int len, const uint64_t (&w)[4], int (&r)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = 0;
+    while (len > 1) { // the rank lies in [r, r + len]
+        const int half = len >> 1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] += s[bt_phys(first + r[k] + half - 1)] < w[k] ? half : 0;
+        len -= half;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] += s[bt_phys(first + r[k])] < w[k] ? 1 : 0;
+}
+
+// One wave sorts the list of n entries at sw[0 .. n) and writes it to keys / vals (the list's output segment).
+// H == 0: pad to a power of two >= 64, one network, written in order.
+// H > 0 (bn_list_words): H < n <= H + H / 4; head = the first H entries, tail = the other T = n - H <= H / 4. The tail has no
+// power-of-two region of its own: it is sorted in the head's first Pt = pow2(T) >= 64 words, whose contents wait meanwhile in
+// the first Pt words of the list's own output segment - nobody else touches it, it is written for good only at the end, and a
+// lane reads back the words it wrote itself. (Held in registers instead, Pt / 64 words per lane, they are live across the
+// network and the kernel no longer fits the 64 VGPRs of eight waves per SIMD: 176 bytes of scratch per lane.) Then the head is
+// sorted in place and the runs are merged on the way out. Keys of one tile are unique - a row enters a tile once -, so the
+// unsigned order is total and index + rank in the other run is a permutation of [0, n). Both runs go through the ONE call
+// site of each network below: the kernel holds two networks, as before.
+__device__ __forceinline__ void bn_sort_list(uint64_t *sw, int n, int H, bool as_int, int lane, uint64_t *keys, int32_t *vals,
+                                             uint64_t hi)
+{
+    const int T = n - H; // H == 0: the whole list
+    int lt = 6;
+    while ((1 << lt) < T) ++lt;
+    const int Pt       = 1 << lt;
+    const uint64_t pad = as_int ? kBtPadInt : kBtPadF64;
+    for (int pass = 0; pass < (H ? 2 : 1); ++pass) {
+        int lp = lt;
+        if (H == 0) {
+            for (int i = n + lane; i < Pt; i += 64) sw[bt_phys(i)] = pad;
+        } else if (pass == 0) { // the tail moves into the head's first Pt words
+            for (int i = lane; i < Pt; i += 64) {
+                keys[i]        = sw[bt_phys(i)];
+                sw[bt_phys(i)] = i < T ? sw[bt_phys(H + i)] : pad;
+            }
+        } else { // the sorted tail goes home, the head's words come back (every lane moves the words it parked)
+            for (int i = lane; i < Pt; i += 64) {
+                const uint64_t tv = sw[bt_phys(i)];
+                sw[bt_phys(i)]    = keys[i];
+                if (i < T) sw[bt_phys(H + i)] = tv;
+            }
+            lp = 31 - __builtin_clz((unsigned)H);
+        }
+        wave_lds_sync();
+        if (as_int) bt_sort_int<64>(sw, lp, lane, [] { wave_lds_sync(); });
+        else bt_sort_f64<64>(sw, lp, lane, [] { wave_lds_sync(); });
+    }
+    if (H == 0) {
+        for (int i = lane; i < n; i += 64) {
+            const uint64_t w = sw[bt_phys(i)];
+            keys[i]          = hi | (w >> 32);
+            vals[i]          = (int32_t)(uint32_t)w;
+        }
+        return;
+    }
+    // merge on the way out: four elements per lane and trip
+    for (int i0 = 0; i0 < H; i0 += 256) { // H is a multiple of 256
+        uint64_t w[4];
+        int r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = sw[bt_phys(i0 + 64 * k + lane)];
+        bn_rank4(sw, H, T, w, r);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int pos = i0 + 64 * k + lane + r[k];
+            keys[pos]     = hi | (w[k] >> 32);
+            vals[pos]     = (int32_t)(uint32_t)w[k];
+        }
+    }
+    for (int j0 = 0; j0 < T; j0 += 256) {
+        uint64_t w[4];
+        int r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = j0 + 64 * k + lane;
+            w[k]        = j < T ? sw[bt_phys(H + j)] : 0ull;
+        }
+        bn_rank4(sw, 0, H, w, r);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = j0 + 64 * k + lane;
+            if (j < T) {
+                keys[j + r[k]] = hi | (w[k] >> 32);
+                vals[j + r[k]] = (int32_t)(uint32_t)w[k];
+            }
+        }
+    }
+}
+
+// Residency: a workgroup is 8 waves and 38.7 KiB of LDS, so four fit a CU - when a wave holds at most 64 VGPRs and 80 SGPRs
+// (gfx950 admits floor(800 / (round_up(sgprs, 16) + 16)) waves per SIMD: 8 up to 80, 7 up to 96, 6 at the 106 this kernel had,
+// i.e. three workgroups per CU and two rounds for c3's 1020 bins). The attribute holds the compiler to that; the tile's
+// uniform state is read as scalars so that what it spills are SGPRs into VGPR lanes, not VGPRs into scratch.
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) bin_sort_kernel(const BinArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const BinGeom &g = a.g;
@@ -591,8 +713,8 @@ __global__ void __launch_bounds__(1024) bin_sort_kernel(const BinArgs a)
     if (e0 == e1) return;
     const uint32_t img = bin / g.n_bins, lb = bin % g.n_bins;
     const uint32_t tx0 = (lb % g.bins_x) * g.bw, ty0 = (lb / g.bins_x) * g.bh;
-    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // uniform, and known to be: a tile's state is scalar
     if ((int)threadIdx.x < 16) {
         const int t       = (int)threadIdx.x;
         const uint32_t tx = tx0 + (uint32_t)t % g.bw, ty = ty0 + (uint32_t)t / g.bw;
@@ -603,11 +725,8 @@ __global__ void __launch_bounds__(1024) bin_sort_kernel(const BinArgs a)
         s_goff[t]         = in ? a.isect_offsets[gid] : 0;
         s_hi[t]           = in ? ((((uint64_t)img << g.tile_bits) | ((uint64_t)ty * g.tile_w + tx)) << 32) : 0ull;
         // cut the arena: tile t of batch s_batch[t] sorts at physical word s_base[t] (16 lanes of the first wave)
-        int P = 0;
-        if (n > 0) {
-            P = 64;
-            while (P < n) P <<= 1;
-        }
+        int head;
+        int P = bn_list_words(n, head);
         const bool big = P > arena_words;
         if (big) P = 0;
         int batch = 0, used = 0, my_batch = n > 0 ? 0 : -1, my_base = 0;
@@ -627,8 +746,7 @@ __global__ void __launch_bounds__(1024) bin_sort_kernel(const BinArgs a)
     for (int b = 0; b < n_batch; ++b) {
         if (threadIdx.x < 16) s_cur[threadIdx.x] = 0;
         if (threadIdx.x == 16) s_odd = a.sort_int ? 0xFFFFu : 0u;
-        uint32_t bmask = 0;
-        for (int t = 0; t < n_bits; ++t) bmask |= (s_batch[t] == b) ? (1u << t) : 0u;
+        const uint32_t bmask = (uint32_t)__builtin_amdgcn_ballot_w64(lane < n_bits && s_batch[lane & 15] == b); // this batch's tiles
         __syncthreads();
         // deal every entry to the lists of the tiles in its mask (LDS cursor per tile). (Round 5: requesting several trips'
         // entries together, or a group ahead, changes nothing - 70.6 .. 71.9 us for 1 / 2 / 4 / 8 trips -: with eight waves per
@@ -648,23 +766,15 @@ __global__ void __launch_bounds__(1024) bin_sort_kernel(const BinArgs a)
         }
         __syncthreads();
         if (wave < n_bits && s_batch[wave] == b) { // one wave per tile: pad, sort, write
-            uint64_t *sw = s_arena + s_base[wave];
-            const int n  = s_tcnt[wave];
-            int lp = 6;
-            while ((1 << lp) < n) ++lp;
-            const bool as_int = (s_odd >> wave) & 1u; // wave-uniform
-            const uint64_t pad = as_int ? kBtPadInt : kBtPadF64;
-            for (int i = n + lane; i < (1 << lp); i += 64) sw[bt_phys(i)] = pad;
-            wave_lds_sync();
-            if (as_int) bt_sort_int<64>(sw, lp, lane, [] { wave_lds_sync(); });
-            else bt_sort_f64<64>(sw, lp, lane, [] { wave_lds_sync(); });
-            const int64_t off = s_goff[wave];
-            const uint64_t hi = s_hi[wave];
-            for (int i = lane; i < n; i += 64) {
-                const uint64_t w    = sw[bt_phys(i)];
-                a.keys_out[off + i] = hi | (w >> 32);
-                a.vals_out[off + i] = (int32_t)(uint32_t)w;
-            }
+            // wave-uniform values read from LDS, as scalars
+            uint64_t *sw = s_arena + __builtin_amdgcn_readfirstlane(s_base[wave]);
+            const int n  = __builtin_amdgcn_readfirstlane(s_tcnt[wave]);
+            const bool as_int = (__builtin_amdgcn_readfirstlane((int)s_odd) >> wave) & 1;
+            const int64_t off = __builtin_amdgcn_readfirstlane(s_goff[wave]);
+            const uint64_t hi = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(s_hi[wave] >> 32)) << 32; // low half: 0
+            int head;
+            bn_list_words(n, head);
+            bn_sort_list(sw, n, head, as_int, lane, a.keys_out + off, a.vals_out + off, hi);
         }
         __syncthreads(); // the arena is cut anew for the next batch
     }
@@ -673,7 +783,8 @@ __global__ void __launch_bounds__(1024) bin_sort_kernel(const BinArgs a)
         if (s_batch[t] != -2) continue;
         if (threadIdx.x == 0) s_n = 0;
         __syncthreads();
-        const int64_t off = s_goff[t];
+        const int64_t off      = s_goff[t];
+        const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
         for (int32_t base = e0; base < e1; base += n_thr) {
             const int32_t e    = base + (int32_t)threadIdx.x;
             const bool has     = e < e1 && (((uint32_t)a.b.e_mask[e] >> t) & 1u);
@@ -870,8 +981,8 @@ static int binned_decide(int64_t rows, uint32_t n_images, uint32_t tile_w, uint3
     if (force && force[0] == 'b') return 1;
     // measured (MI355X, profiles/r07_ab.md): 1 M rows x 8160 tiles (c3) 0.214 vs 0.249 ms; 4 M rows per image (c4:
     // ~1800 entries per tile, one wave sorting 2048 words) 4.3 vs 2.5 ms -> dense images and small calls stay Gaussian-major
-    // What decides is the typical tile list: one wave sorts a list padded to a power of two, and the eight lists of a bin share
-    // a 4096-word arena - lists of up to 512 entries (c3: 122 rows per tile, 466 per list) fit in one go. Uniform scene,
+    // What decides is the typical tile list: one wave sorts a list padded to a power of two (or split: bn_list_words), and the
+    // eight lists of a bin share a 4352-word arena - lists of around 512 entries (c3: 122 rows per tile, 466 per list) fit in one go. Uniform scene,
     // fused vs binned in ms (tools/gpu_isect_sizes.py): 250 k rows 0.141 / 0.103, 600 k 0.189 / 0.156, 1 M 0.245 / 0.209,
     // 2 M (245 rows per tile, lists of ~930) 0.399 / 0.470; four cameras: 4 x 250 k 0.265 / 0.222, 4 x 1 M 0.757 / 0.584.
     // Clustered scenes are caught by the skew test (bn_overflow); very small calls (garden x1, 112 k clustered rows: 0.17 / 0.29)
@@ -907,8 +1018,9 @@ static int binned_setup(const char *fn, BinArgs &a, int64_t rows, uint32_t n_ima
     GSX_REQUIRE(bin_geometry(a.g, rows, n_images, tile_size, tile_w, tile_h, bin_cap_entries(rows)),
                 "%s: %u images x %u x %u tiles not supported", fn, n_images, tile_w, tile_h);
     a.sort_int = bitonic_f64_enabled() ? 0u : 1u;
-    // skew abort: 3/4 of the sort arena's words (a c3 bin of 4x2 tiles holds ~1400 entries, its longest ~1700); not when the
-    // path was forced (tests drive the big-list code with it)
+    // skew abort: 3/4 of the sort arena's words (a c3 bin of 4x2 tiles holds ~1400 entries, its longest ~1700) - a share of the
+    // arena on purpose: a bin is crowded in proportion to what one batch can hold; not when the path was forced (tests drive
+    // the big-list code with it)
     {
         const char *force = getenv("GSX_ISECT_PATH");
         a.g.skew_cap = (force && force[0] == 'b') ? 0 : (int32_t)(kArenaPerWave * (int)(a.g.bw * a.g.bh) * 3 / 4);
@@ -1006,8 +1118,10 @@ extern "C" int gsx_isect_binned_emit_sort(int64_t rows, uint32_t n_images, uint3
     t.bucketed = a.bucketed; t.scratch = scratch;
     t.big_count = &a.b.hdr->big_count; t.big_list = a.b.big_list;
     t.keys_out = a.keys_out; t.vals_out = a.vals_out;
-    // every list sorts inside bin_sort's arena when its power-of-two padding fits: a caller that knows the longest list (the
-    // count half reported it) spares the launch of the (then empty) work-list sort - 4 us of a 147 KiB-LDS grid spinning up
+    // every list sorts inside bin_sort's arena when its region fits, and a list of n <= arena / 2 entries does whatever the
+    // arena's size (n rounded up to a power of two is below the arena, bn_list_words(n) never above that): a caller that knows
+    // the longest list (the count half reported it) spares the launch of the (then empty) work-list sort - 4 us of a
+    // 147 KiB-LDS grid spinning up
     if (longest_list > 0 && longest_list <= (int64_t)(kArenaPerWave * n_bits) / 2) return GSX_OK;
     return launch_big_tile_sort(t, s);
 }
