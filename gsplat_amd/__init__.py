@@ -42,6 +42,8 @@ _LAZY = {
     "color_correct_affine": "color_correct", "color_correct_quadratic": "color_correct", "color_correct": "color_correct",
     # the per-Gaussian appearance MLP of the trainer's app_opt path (examples/utils.py: AppearanceOptModule)
     "AppearanceOptModule": "appearance", "appearance": "appearance",
+    # the deformation network of the dynamic-scene trainer (gsplat/contrib/dynamic/deformation.py)
+    "DeformNetwork": "deformation", "DeformationTable": "deformation", "deformation": "deformation",
     # before step 0: the nearest-neighbour scale initialisation (gsplat/init_utils.py, examples/utils.py: knn)
     "knn": "init_utils", "knn_scale_init": "init_utils", "init_utils": "init_utils",
     # on-disk formats

@@ -270,6 +270,10 @@ def appearance_bwd_workspace_floats(n: int, n_cameras: int) -> int:
     return int(_lib.gsx_appearance_bwd_workspace_floats(n, n_cameras))
 
 
+def deform_bwd_workspace_floats(n: int) -> int:
+    return int(_lib.gsx_deform_bwd_workspace_floats(n))
+
+
 def knn_workspace_bytes(n: int, k: int) -> int:
     return int(_lib.gsx_knn_workspace_bytes(n, k))
 

@@ -1095,6 +1095,30 @@ int gsx_appearance_bwd(const float *features, const float *dirs, const int64_t *
                        void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Deformation network of the dynamic-scene trainer (gsplat/contrib/dynamic/deformation.py: DeformNetwork with feature_dim 64,
+ * hidden_dim 64, num_layers 3): h = relu(W3 relu(W2 relu(W1 x + b1) + b2) + b3) over a Gaussian's plane features x,
+ * d = W_head h + b_head = [position 3 | quaternion 4 | opacity 1], outputs (means + d[0:3], quats + d[3:7], opacities + d[7]).
+ * All float32 and contiguous: plane_features [N, 64], 16-byte aligned; means [N, 3], quats [N, 4], opacities [N, 1]; W1, W2, W3
+ * [64, 64]; b1, b2, b3 [64]; W_head [8, 64] and b_head [8], the three heads joined in the order above. 0 < N < 2^31.
+ * fwd: one launch; means_out, quats_out, opacities_out: every element written.
+ * bwd (recomputes the forward): v_means_out [N, 3], v_quats_out [N, 4], v_opacities_out [N, 1], the cotangents of the three
+ * outputs, each may be NULL = zeros (they are also the gradients of means, quats and opacities: the caller passes them on).
+ * workspace [gsx_deform_bwd_workspace_floats(N)] is scratch. Written, every element: v_plane_features [N, 64], 16-byte aligned,
+ * or NULL (not wanted: that product is skipped); v_W [3, 64, 64] = the gradients of W1, W2, W3; v_small [712] = v_b1 [64] |
+ * v_b2 [64] | v_b3 [64] | v_W_head [8, 64] | v_b_head [8].
+ * No float atomics: per-wave and per-workgroup partial sums (gsx_deform_blocks(N) workgroups) added in a fixed order, in double,
+ * so repeats are bit-equal. */
+int64_t gsx_deform_blocks(int64_t N);
+int64_t gsx_deform_bwd_workspace_floats(int64_t N);
+int gsx_deform_fwd(const float *means, const float *quats, const float *opacities, const float *plane_features, const float *W1,
+                   const float *b1, const float *W2, const float *b2, const float *W3, const float *b3, const float *W_head,
+                   const float *b_head, int64_t N, float *means_out, float *quats_out, float *opacities_out, void *stream);
+int gsx_deform_bwd(const float *plane_features, const float *W1, const float *b1, const float *W2, const float *b2,
+                   const float *W3, const float *b3, const float *W_head, const float *b_head, int64_t N,
+                   const float *v_means_out, const float *v_quats_out, const float *v_opacities_out, float *workspace,
+                   float *v_plane_features, float *v_W, float *v_small, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact k-nearest-neighbour search of a point cloud against itself, the kernel of the scale initialisation every reference
  * trainer starts with: gsplat/init_utils.py:145 knn_scale_init (chunked torch.cdist + topk, O(N^2)) and examples/utils.py:156
  * knn (scikit-learn NearestNeighbors(n_neighbors=K).fit(x).kneighbors(x) on the host; simple_trainer.py:321).
