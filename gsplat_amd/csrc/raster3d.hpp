@@ -370,7 +370,7 @@ __device__ __forceinline__ float staged_e_offset(const float4 &ga, const float2 
 struct StagedRow { // one staged Gaussian in LDS: 48 bytes, read as b128 + b128 + b64 from ONE address register
     v4f p0;        // ax, ay (mean - tile centre), lo (base of the exponent), lo (reject level: e > lo <=> sigma < 0)
     v4f p1;        // nA, nB, nC, colour 2
-    v4f p2;        // colour 0, colour 1, colour 3, -
+    v4f p2;        // colour 0, colour 1, colour 3, - (variant W of the backward: the flatten id, as bits)
 };
 __device__ __forceinline__ void stage_gaussian_f(float ax, float ay, float opac, float ca, float cb, float cc, v4f &p0,
                                                  float &nA, float &nB, float &nC)

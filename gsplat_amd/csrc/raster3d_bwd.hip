@@ -671,8 +671,14 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
 //     Gaussian did not reach skip their reads, the 16 lanes of a slot are one DPP row: a row all-reduce gives every lane
 //     the K totals, and lane c of the row turns them into column c of the gradient row and adds it to HBM - consecutive
 //     lanes, consecutive floats of one row. No accumulator table, no LDS atomics, no re-zeroing, no separate flush pass.
-// LDS per wave: 64 x (48 + 16) B staged + 4 slots x 2304 B of W = 13.3 KB -> 12 waves per CU, each with up to 168 VGPRs;
+//     The conversion is branch-free: columns of one form share it through operand selects, the lane keeps its own result.
+// LDS per wave: 64 x 48 B staged + 4 slots x 2304 B of W = 12 KiB. The staged row is all a turn needs of a Gaussian: its
+// mean's offset is p0.x / p0.y, and the flatten id rides in the spare word p2.w as bits (never touched by arithmetic). The
+// runtime admits 12 workgroups per CU for the 3-channel kernel at 12 or 13 KiB alike - the 168-VGPR budget of three waves per
+// SIMD binds, not the LDS (profiles/r14_bwd_chain.md);
 // the four independent pixel chains per lane give the instruction-level parallelism that variant T gets from occupancy.
+// The slot bookkeeping of the walk stays at run time: one copy of the walk per slot (lane select and parked-store offset as
+// constants) was built and is slower - the copies hand T / behind to each other through eight moves per contributor (same document).
 // CH <= 4, 16 x 16 tiles, no absgrad (as variant T).
 #ifndef GSX_BWD_W_WAVES
 #define GSX_BWD_W_WAVES 3
@@ -690,7 +696,7 @@ struct BwdWCfg {
     static constexpr int GP    = 36;     // floats per group of 16 pixels (two rows of a quadrant): 16 x (fac, w) + 4 (bank spread)
     static constexpr int QP    = 4 * GP; // per quadrant
     static constexpr int SP    = 4 * QP; // per slot
-    static constexpr size_t smem = (size_t)BATCH * (sizeof(StagedRow) + sizeof(float4)) + sizeof(float) * SLOTS * SP;
+    static constexpr size_t smem = (size_t)BATCH * sizeof(StagedRow) + sizeof(float) * SLOTS * SP;
 };
 
 template <int CH, bool ABS>
@@ -708,8 +714,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     StagedRow *s_st = reinterpret_cast<StagedRow *>(smem_raw);  // staged offset form of the exponent + colours (raster3d.hpp)
-    float4 *s_aux   = reinterpret_cast<float4 *>(s_st + BATCH); // mean - tile centre (x, y), flatten id (bits), -
-    float *s_w      = reinterpret_cast<float *>(s_aux + BATCH); // [SLOTS][4 quadrants][4 groups][GP]: (fac, w) per pixel
+    float *s_w      = reinterpret_cast<float *>(s_st + BATCH);  // [SLOTS][4 quadrants][4 groups][GP]: (fac, w) per pixel
 
     TileCtx tc;
     if (a.tile_order ? !tile_context_ordered(a, blockIdx.x, tc) : !tile_context(a, blockIdx.x, tc)) return;
@@ -787,6 +792,14 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
     int slot            = 0;      // wave-uniform: slots filled since the last turn
     int slot_info       = 0;      // LANE s (s < SLOTS): staged index << 4 | quadrants that contributed, of the Gaussian in slot s
 
+    // lane c of a slot's 16-lane row owns column c of the gradient row: the geometry columns, then this chunk's channels
+    const int col_c        = (int)(lane & 15u);
+    const bool col_put     = col_c < GEO || col_c - GEO < min(CH, (int)a.nch);
+    const uint32_t col_out = (uint32_t)col_c + (col_c < GEO ? 0u : a.ch_off);
+    // which form a lane keeps in the turn (lane constants; the pair test as a bit mask, which stays a single compare)
+    const bool c_is0 = col_c == 0, c_lt2 = col_c < 2, c_is2 = col_c == 2, c_is3 = col_c == 3, c_is5 = col_c == 5;
+    const bool c_24  = ((1u << col_c) & 0x14u) != 0u;
+
     // one turn: sums of the filled slots -> gradient rows in HBM (all lanes take part)
     auto turn = [&](int n_slots) {
         wave_lds_sync();
@@ -855,36 +868,38 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
         for (int k = 0; k < K; ++k) acc[k] = row16_sum(acc[k]);
         // lane c of the row -> column c of the Gaussian's gradient row. Raw tile-centre moments -> moments of d = mean - pixel
         // = a - (u, v):  S_x = ax S0 - Su, S_xx = ax^2 S0 - 2 ax Su + Suu, S_xy = ax ay S0 - ax Sv - ay Su + Suv, ...
-        const int c = (int)(lane & 15u);
-        if (live && c < NCOL) {
+        // No branch per column: one arm after the other under partial EXEC masks cost seven mask set-ups and branches per turn
+        // on top of the arithmetic. Columns that share a form (0 | 1, 2 | 4) pick their operands with selects, every lane
+        // evaluates the four forms, and a last chain of selects keeps the lane's own. Each column's value comes from the
+        // operations, in the order, of the formula next to it (products that must round on their own are fma addends).
+        if (live && col_put) {
             constexpr float kInvLog2e = 1.0f / kLog2e;
             const int t_g    = info >> 4;
-            const float4 aux = s_aux[t_g];
+            const v4f p0     = s_st[t_g].p0; // ax, ay (mean - tile centre), lo, lo
             const v4f p1     = s_st[t_g].p1; // (-A, -B, -C) of the staged form: Q = (2A, B; B, 2C) / log2(e)
-            const float lo   = s_st[t_g].p0.w;
-            const float ax = aux.x, ay = aux.y;
-            const int32_t id = __float_as_int(aux.z);
+            const float lo   = p0.w;
+            const float ax = p0.x, ay = p0.y;
+            const uint32_t id = (uint32_t)__float_as_int(s_st[t_g].p2.w); // the flatten id rides in the row's spare word, as bits
             const float S0 = acc[CH], Su = acc[CH + 1], Sv = acc[CH + 2];
             const float sx = fmaf(ax, S0, -Su), sy = fmaf(ay, S0, -Sv);
-            float val;
-            int col  = c;
-            bool put = true;
-            if (c == 0) val = -kInvLog2e * (2.0f * p1.x * sx + p1.y * sy);
-            else if (c == 1) val = -kInvLog2e * (p1.y * sx + 2.0f * p1.z * sy);
-            else if (c == 2) val = 0.5f * (ax * (ax * S0 - 2.0f * Su) + acc[CH + 3]);
-            else if (c == 3) val = ax * (ay * S0 - Sv) - ay * Su + acc[CH + 4];
-            else if (c == 4) val = 0.5f * (ay * (ay * S0 - 2.0f * Sv) + acc[CH + 5]);
-            else if (c == 5) val = -S0 * __builtin_amdgcn_exp2f(-lo); // v_opacity = sum vis v_alpha = -S_w / opacity
-            else if (ABS && c < GEO) val = kInvLog2e * (c == 6 ? acc[CH + (ABS ? 6 : 0)] : acc[CH + (ABS ? 7 : 0)]); // sum |v_mean2d|
-            else {
-                const int k = c - GEO;
-                val         = 0.0f;
+            // 0: -(2 nA sx + nB sy) / log2(e)    1: -(nB sx + 2 nC sy) / log2(e)
+            const float v01 = -kInvLog2e * fmaf(p1.y, c_is0 ? sy : sx, (2.0f * (c_is0 ? p1.x : p1.z)) * (c_is0 ? sx : sy));
+            // 2: (ax (ax S0 - 2 Su) + Suu) / 2   4: (ay (ay S0 - 2 Sv) + Svv) / 2
+            const float a24 = c_is2 ? ax : ay;
+            const float v24 = 0.5f * fmaf(a24, fmaf(a24, S0, -(2.0f * (c_is2 ? Su : Sv))), c_is2 ? acc[CH + 3] : acc[CH + 5]);
+            // 3: ax (ay S0 - Sv) - ay Su + Suv
+            const float v3 = acc[CH + 4] + fmaf(ax, sy, -(ay * Su));
+            // 5: v_opacity = sum vis v_alpha = -S_w / opacity
+            const float v5 = -S0 * __builtin_amdgcn_exp2f(-lo);
+            float val = 0.0f;
 #pragma unroll
-                for (int kk = 0; kk < CH; ++kk) val = (k == kk) ? acc[kk] : val;
-                put = k < (int)a.nch;
-                col = GEO + (int)a.ch_off + k;
-            }
-            if (put) atomic_add_f32(a.v_rows + (size_t)id * a.row_stride + col, val);
+            for (int kk = 0; kk < CH; ++kk) val = (col_c == GEO + kk) ? acc[kk] : val;
+            if constexpr (ABS) val = col_c == 6 ? kInvLog2e * acc[CH + (ABS ? 6 : 0)] : col_c == 7 ? kInvLog2e * acc[CH + (ABS ? 7 : 0)] : val; // sum |v_mean2d|
+            val = c_is5 ? v5 : val;
+            val = c_is3 ? v3 : val;
+            val = c_24 ? v24 : val;
+            val = c_lt2 ? v01 : val;
+            atomic_add_f32(a.v_rows + ((uint64_t)id * a.row_stride + col_out), val);
         }
         wave_lds_sync();
     };
@@ -926,8 +941,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
                 const v4f p1 = v4f{nA, nB, nC, f.cv[2]};
                 s_st[lane].p0 = p0;
                 s_st[lane].p1 = p1;
-                s_st[lane].p2 = v4f{f.cv[0], f.cv[1], f.cv[3], 0.0f};
-                s_aux[lane]   = make_float4(ax, ay, __int_as_float(g), 0.0f);
+                s_st[lane].p2 = v4f{f.cv[0], f.cv[1], f.cv[3], __int_as_float(g)};
                 // the two-stage test of the wave-level culling (raster3d.hpp), once per quadrant; a quadrant whose pixels all
                 // stopped in front of this entry cannot be reached either
                 const float2 he = cull_half_extent(opac, ca, cb, cc);
@@ -1011,7 +1025,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
 }
 
 // three waves per SIMD (<= 168 VGPRs) hold the state of one to three channels; four channels (64 cotangent registers per lane)
-// take two waves per SIMD rather than spill
+// are allowed two waves per SIMD rather than spill (with the branch-free conversion the allocator ends at 166, i.e. still three)
 template <int CH>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSX_BWD_W_WAVES)))
 raster3d_bwd_w_kernel(Raster3DArgs a)
