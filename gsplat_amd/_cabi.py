@@ -1,15 +1,16 @@
 """ctypes binding of the C-ABI in include/gsplat_amd.h (libgsplat_amd.so).
 
 This is the only place that crosses from Python into native code. There is NO CPU fallback:
-if the shared library is missing the import fails loudly, and every call targets HIP kernels
-on the current device/stream.
+if the shared library is missing the import fails loudly, and every call targets HIP kernels.
+
+call(name, *args) takes the tensors themselves and marshals them: it holds them until the launch is queued and launches
+on their device's current stream. query(name, *ints) is the host-only twin for the size / capability queries.
 """
 from __future__ import annotations
 
 import ctypes
 import json
 import os
-import threading
 from typing import Optional
 
 import torch
@@ -118,38 +119,35 @@ def exported_symbols():
     return list(SIGNATURES)
 
 
-_tls = threading.local()  # .dev = device index of the tensors marshalled for the next call (per thread: _bwd ops run on
-#                           autograd worker threads)
+def _refuse_host_tensor(t: torch.Tensor) -> None:
+    """The one device rule of this module: a tensor handed to native code that is not on a ROCm device ends here.
+    tools/dry_run.py replaces this function to exercise the host side with CPU tensors."""
+    raise GsplatAmdError("gsplat_amd kernels only run on a ROCm device (got a CPU tensor); there is no CPU fallback")
+
+
+class strided:
+    """Marks a call() argument as a view whose layout the caller has already checked (row-strided views): the device
+    check stays, the contiguity check is skipped."""
+    __slots__ = ("t",)
+
+    def __init__(self, t: torch.Tensor):
+        self.t = t
 
 
 def ptr(t: Optional[torch.Tensor]):
-    """Device pointer of a tensor (None -> NULL). The tensor must be contiguous and on the GPU. Remembers the tensor's
-    device so that call() launches on THAT device's current stream (the reference's DEVICE_GUARD, Common.h:40)."""
+    """Checked data_ptr() of a contiguous device tensor (None -> NULL), for code that drives the library directly. The
+    caller keeps the tensor alive; the launch goes to the current device. Product code passes the tensor to call()."""
     if t is None:
         return None
-    if not t.is_cuda:
-        raise GsplatAmdError(
-            "gsplat_amd kernels only run on a ROCm device (got a CPU tensor); there is no CPU fallback"
-        )
     if not t.is_contiguous():
         raise GsplatAmdError("gsplat_amd: tensor must be contiguous")
-    _tls.dev = t.device.index
-    return t.data_ptr()
-
-
-def ptr_host(t: torch.Tensor):
-    """Address of a PINNED host tensor, for the few scalar results a kernel writes straight into host memory (pinned
-    memory is mapped into the device's address space: no device-to-host copy kernel is needed for 8 bytes)."""
-    if t.is_cuda or not t.is_pinned():
-        raise GsplatAmdError("gsplat_amd: expected a pinned host tensor")
-    return t.data_ptr()
+    return ptr_strided(t)
 
 
 def ptr_strided(t: torch.Tensor):
-    """Device pointer of a tensor whose layout the caller has already checked (row-strided views)."""
+    """The same for a tensor whose layout the caller has already checked (row-strided views)."""
     if not t.is_cuda:
-        raise GsplatAmdError("gsplat_amd kernels only run on a ROCm device (got a CPU tensor); there is no CPU fallback")
-    _tls.dev = t.device.index
+        _refuse_host_tensor(t)
     return t.data_ptr()
 
 
@@ -233,15 +231,47 @@ def profile_end() -> dict:
     return out
 
 
+_SCALARS = frozenset((int, float, bool))
+
+
 def call(name: str, *args) -> None:
-    """Invoke a gsx_* entry point on the current stream of the device that owns the tensors marshalled by ptr() for it
-    (device guard: if that is not the current device it becomes current for the duration of the launch); raise on a
-    non-zero return code."""
-    dev = getattr(_tls, "dev", None)
-    if dev is not None and dev != torch.cuda.current_device():
-        _tls.dev = None
+    """Invoke a gsx_* entry point on the current stream of the device that owns its tensor arguments; raise on a non-zero
+    return code. A torch.Tensor (contiguous, on a ROCm device), None (NULL) or strided(view) stands at a pointer
+    position; anything else (int, float, ctypes array, raw address) passes through. `args` references the tensors until
+    the entry point has returned, i.e. until the launch is queued, so a temporary (`x.contiguous()`) in the argument list
+    is safe. Device guard: tensors on two devices are an error; if their device is not the current one it becomes current
+    for the duration of the launch; without tensor arguments the launch goes to the current device."""
+    codes = SIGNATURES[name][1]  # the last one is the stream
+    if len(args) + 1 != len(codes):
+        raise TypeError(f"{name}: takes {len(codes) - 1} arguments before the stream, got {len(args)}")
+    raw, dev = list(args), -1
+    for i, a in enumerate(args):
+        if type(a) in _SCALARS:  # the one test most arguments take
+            continue
+        if a is not None:
+            if type(a) is strided:
+                a = a.t
+            elif not isinstance(a, torch.Tensor):
+                continue  # a ctypes array or pointer
+            elif not a.is_contiguous():
+                raise GsplatAmdError("gsplat_amd: tensor must be contiguous")
+            if not a.is_cuda:
+                _refuse_host_tensor(a)
+            d = a.get_device()
+            if d != dev:
+                if dev >= 0 and d >= 0:
+                    raise GsplatAmdError(f"{name}: tensor arguments on two devices (cuda:{dev} and cuda:{d}, argument {i})")
+                dev = d
+            raw[i] = a.data_ptr()
+        if codes[i] != "p":
+            raise TypeError(f"{name}: argument {i} is a '{codes[i]}' scalar, got {type(args[i]).__name__}")
+    if dev >= 0 and dev != torch.cuda.current_device():
         with torch.cuda.device(dev):
-            return call(name, *args)
+            return _launch(name, raw)
+    _launch(name, raw)
+
+
+def _launch(name: str, args) -> None:
     fn = getattr(_lib, name)
     if _profile is not None and (_profile_only is None or name in _profile_only):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -258,44 +288,26 @@ def call(name: str, *args) -> None:
         raise GsplatAmdError(f"{name} failed (code {rc}): {msg}")
 
 
+def query(name: str, *ints) -> int:
+    """A size / capability query of the library (gsx_*_workspace_bytes, gsx_*_blocks, ...): host-only, no stream."""
+    return int(getattr(_lib, name)(*ints))
+
+
+# the workspace sizes that tests/test_gpu_sort_edges.py and tests/test_gpu_ops.py ask for by these names
 def scan_workspace_bytes(n: int) -> int:
-    return int(_lib.gsx_scan_workspace_bytes(n))
+    return query("gsx_scan_workspace_bytes", n)
 
 
 def sort_workspace_bytes(n: int) -> int:
-    return int(_lib.gsx_sort_pairs_workspace_bytes(n))
+    return query("gsx_sort_pairs_workspace_bytes", n)
 
 
-def appearance_bwd_workspace_floats(n: int, n_cameras: int) -> int:
-    return int(_lib.gsx_appearance_bwd_workspace_floats(n, n_cameras))
-
-
-def deform_bwd_workspace_floats(n: int) -> int:
-    return int(_lib.gsx_deform_bwd_workspace_floats(n))
-
-
-def knn_workspace_bytes(n: int, k: int) -> int:
-    return int(_lib.gsx_knn_workspace_bytes(n, k))
-
-
-def kmeans_workspace_bytes(n: int, d: int, k: int) -> int:
-    return int(_lib.gsx_kmeans_workspace_bytes(n, d, k))
-
-
-def plas_workspace_bytes(h: int, w: int, c: int) -> int:
-    return int(_lib.gsx_plas_workspace_bytes(h, w, c))
-
-
-def plas_partials_floats(h: int, w: int) -> int:
-    return int(_lib.gsx_plas_partials_floats(h, w))
+def tile_sort_workspace_bytes(n: int, n_images: int, tile_w: int, tile_h: int) -> int:
+    return query("gsx_isect_tile_sort_workspace_bytes", n, n_images, tile_w, tile_h)
 
 
 def tile_sort_supported(n_images: int, tile_w: int, tile_h: int) -> bool:
     return bool(_lib.gsx_isect_tile_sort_supported(n_images, tile_w, tile_h))
-
-
-def tile_sort_workspace_bytes(n: int, n_images: int, tile_w: int, tile_h: int) -> int:
-    return int(_lib.gsx_isect_tile_sort_workspace_bytes(n, n_images, tile_w, tile_h))
 
 
 def isect_fused_supported(n_images: int, tile_w: int, tile_h: int, packed: bool) -> bool:
@@ -370,8 +382,6 @@ def copy_message_columns(msg_ptr: int, msg_stride: int, rows: int, groups, to_me
 def sort_pairs(keys, vals, keys_alt, vals_alt, n: int, end_bit: int, workspace) -> bool:
     """Returns True when the sorted data ended up in the alt buffers."""
     flag = ctypes.c_int(0)
-    rc = _lib.gsx_sort_pairs(ptr(keys), ptr(vals), ptr(keys_alt), ptr(vals_alt), n, end_bit, ptr(workspace),
-                             workspace.numel() * workspace.element_size(), ctypes.addressof(flag), current_stream())
-    if rc != 0:
-        raise GsplatAmdError(f"gsx_sort_pairs failed (code {rc}): {_lib.gsx_last_error().decode(errors='replace')}")
+    call("gsx_sort_pairs", keys, vals, keys_alt, vals_alt, n, end_bit, workspace, workspace.numel() * workspace.element_size(),
+         ctypes.addressof(flag))
     return bool(flag.value)

@@ -25,7 +25,7 @@ import torch
 from torch import Tensor
 
 from . import _cabi
-from ._cabi import call, ptr, ptr_strided
+from ._cabi import call, strided
 
 NS = "gsplat"
 
@@ -69,7 +69,7 @@ SEG_MIN_LONGEST = 2 * SEG_LEN if SEG_LEN > 0 else 1 << 62  # lower bound of the 
 
 def _seg_cut(n_isects: int, n_images: int, tw: int, th: int) -> int:
     """Lists longer than this are cut into slices: max(2 slices, 3 x the mean list) - segments are for outliers."""
-    return _cabi._lib.gsx_raster3d_seg_cut(int(n_isects), int(n_images), int(tw), int(th), SEG_LEN) if SEG_LEN > 0 else 1 << 62
+    return _cabi.query("gsx_raster3d_seg_cut", int(n_isects), int(n_images), int(tw), int(th), SEG_LEN) if SEG_LEN > 0 else 1 << 62
 
 
 _lookup_longest = torch.ops.gsplat_amd.lookup_longest.default  # (flatten_ids) -> int; the overload: no resolution per call
@@ -254,7 +254,7 @@ def _packed_row_map(batch_ids, camera_ids, gaussian_ids, B: int, C: int, N: int)
             if k == key:
                 return rm
     row_map = torch.empty(B * C * N, device=gaussian_ids.device, dtype=torch.int32)
-    call("gsx_packed_row_map", ptr(ids[0]), ptr(ids[1]), ptr(ids[2]), gaussian_ids.shape[0], B, C, N, ptr(row_map))
+    call("gsx_packed_row_map", ids[0], ids[1], ids[2], gaussian_ids.shape[0], B, C, N, row_map)
     with _row_map_lock:
         _row_map_cache[:] = [(key, ids, row_map)]
     return row_map
@@ -288,8 +288,8 @@ def quat_scale_to_covar_preci(quats, scales, compute_covar, compute_preci, triu)
     tail = (6,) if triu else (3, 3)
     covars = torch.empty(batch + tail, device=quats.device, dtype=quats.dtype) if compute_covar else None
     precis = torch.empty(batch + tail, device=quats.device, dtype=quats.dtype) if compute_preci else None
-    call("gsx_quat_scale_to_covar_fwd_f64" if f64 else "gsx_quat_scale_to_covar_fwd", ptr(quats), ptr(scales), n, int(triu),
-         ptr(covars), ptr(precis))
+    call("gsx_quat_scale_to_covar_fwd_f64" if f64 else "gsx_quat_scale_to_covar_fwd", quats, scales, n, int(triu),
+         covars, precis)
     return covars, precis
 
 
@@ -299,8 +299,8 @@ def quat_scale_to_covar_preci_bwd(quats, scales, triu, v_covars, v_precis):
     quats, scales = quats.contiguous(), scales.contiguous()
     n = math.prod(quats.shape[:-1])
     v_quats, v_scales = torch.empty_like(quats), torch.empty_like(scales)
-    call("gsx_quat_scale_to_covar_bwd_f64" if f64 else "gsx_quat_scale_to_covar_bwd", ptr(quats), ptr(scales), n, int(triu),
-         ptr(_c(v_covars)), ptr(_c(v_precis)), ptr(v_quats), ptr(v_scales))
+    call("gsx_quat_scale_to_covar_bwd_f64" if f64 else "gsx_quat_scale_to_covar_bwd", quats, scales, n, int(triu),
+         _c(v_covars), _c(v_precis), v_quats, v_scales)
     return v_quats, v_scales
 
 
@@ -418,15 +418,14 @@ def spherical_harmonics(degrees_to_use, means, viewmats, coeffs, masks, batch_id
     if packed:
         nnz = gaussian_ids.shape[0]
         colors = torch.empty((nnz, D), device=means.device, dtype=means.dtype)
-        call("gsx_sh_fwd", degrees_to_use, ptr(means), ptr(viewmats), ptr(coeffs), ptr(masks), ptr(_c(batch_ids)),
-             ptr(_c(camera_ids)), ptr(_c(gaussian_ids)), B, C, N, nnz, int(_gathered), K, D, ptr(_c(_radii)),
-             int(_post), ptr(colors))
+        call("gsx_sh_fwd", degrees_to_use, means, viewmats, coeffs, masks, _c(batch_ids), _c(camera_ids), _c(gaussian_ids), B,
+             C, N, nnz, int(_gathered), K, D, _c(_radii), int(_post), colors)
     else:
         if coeffs.shape[0] != N:
             raise ValueError("means N must match coeffs N in dense mode")
         colors = torch.empty(viewmats.shape[:-2] + (N, D), device=means.device, dtype=means.dtype)
-        call("gsx_sh_fwd", degrees_to_use, ptr(means), ptr(viewmats), ptr(coeffs), ptr(masks), None, None, None,
-             B, C, N, -1, 1, K, D, ptr(_c(_radii)), int(_post), ptr(colors))
+        call("gsx_sh_fwd", degrees_to_use, means, viewmats, coeffs, masks, None, None, None,
+             B, C, N, -1, 1, K, D, _c(_radii), int(_post), colors)
     return colors
 
 
@@ -474,10 +473,9 @@ def spherical_harmonics_bwd(degrees_to_use, means, viewmats, coeffs, masks, batc
     if compute_v_viewmats:
         n_rows = nnz if packed else B * C * N
         v_dirs = torch.zeros((n_rows, 3), device=means.device, dtype=means.dtype)
-    call("gsx_sh_bwd", degrees_to_use, ptr(means), ptr(viewmats), ptr(coeffs), ptr(masks), ptr(_c(batch_ids)),
-         ptr(_c(camera_ids)), ptr(_c(gaussian_ids)), B, C, N, nnz, int(_gathered) if packed else 1, K, D,
-         ptr(_c(_radii)), ptr(_c(_post_colors)), ptr_strided(v_colors), vc_stride, ptr(row_map), ptr(v_coeffs),
-         ptr(v_means), ptr(v_dirs))
+    call("gsx_sh_bwd", degrees_to_use, means, viewmats, coeffs, masks, _c(batch_ids), _c(camera_ids), _c(gaussian_ids), B, C, N,
+         nnz, int(_gathered) if packed else 1, K, D, _c(_radii), _c(_post_colors), strided(v_colors), vc_stride, row_map,
+         v_coeffs, v_means, v_dirs)
     v_viewmats = None
     if compute_v_viewmats:
         if packed:
@@ -501,8 +499,8 @@ def _scan_i32(x: Tensor) -> Tensor:
     """Inclusive int64 prefix sum of an int32 tensor (flattened)."""
     n = x.numel()
     out = torch.empty(n, device=x.device, dtype=torch.int64)
-    ws = torch.empty(max(_cabi.scan_workspace_bytes(n), 8), device=x.device, dtype=torch.uint8)
-    call("gsx_scan_i32", ptr(x), n, ptr(out), ptr(ws), ws.numel())
+    ws = torch.empty(max(_cabi.query("gsx_scan_workspace_bytes", n), 8), device=x.device, dtype=torch.uint8)
+    call("gsx_scan_i32", x, n, out, ws, ws.numel())
     return out
 
 
@@ -578,11 +576,11 @@ def isect_begin(means2d, radii, depths, conics, opacities, image_ids, gaussian_i
         raise RuntimeError("isect_begin: a tile_mask needs the fused path (sort=True, float32, isect_fused_supported)")
     st.host_total = torch.zeros(1, dtype=torch.int64, pin_memory=True)  # n_isects
     if f64:
-        call("gsx_isect_count_f64", ptr(means2d), ptr(radii), ptr(image_ids), rows, n_per, I, tile_size, tile_width,
-             tile_height, ptr(st.tiles_per_gauss))
+        call("gsx_isect_count_f64", means2d, radii, image_ids, rows, n_per, I, tile_size, tile_width,
+             tile_height, st.tiles_per_gauss)
     else:
-        call("gsx_isect_count", ptr(means2d), ptr(radii), ptr(conics), ptr(opacities), ptr(image_ids), rows, n_per, I,
-             tile_size, tile_width, tile_height, ptr(st.tiles_per_gauss))
+        call("gsx_isect_count", means2d, radii, conics, opacities, image_ids, rows, n_per, I,
+             tile_size, tile_width, tile_height, st.tiles_per_gauss)
     st.cum = _scan_i32(st.tiles_per_gauss)
     st.host_total[:1].copy_(st.cum[-1:], non_blocking=True)
     st.event = torch.cuda.Event()
@@ -615,11 +613,11 @@ def isect_finish(st: "_IsectPending"):
     if n_isects == 0:
         return tiles_per_gauss, isect_ids, flatten_ids
     if means2d.dtype == torch.float64:
-        call("gsx_isect_emit_f64", ptr(means2d), ptr(radii), ptr(depths), ptr(image_ids), ptr(cum), rows, n_per, I,
-             tile_size, tile_width, tile_height, ptr(isect_ids), ptr(flatten_ids))
+        call("gsx_isect_emit_f64", means2d, radii, depths, image_ids, cum, rows, n_per, I,
+             tile_size, tile_width, tile_height, isect_ids, flatten_ids)
     else:
-        call("gsx_isect_emit", ptr(means2d), ptr(radii), ptr(depths), ptr(conics), ptr(opacities), ptr(image_ids),
-             ptr(cum), rows, n_per, I, tile_size, tile_width, tile_height, ptr(isect_ids), ptr(flatten_ids))
+        call("gsx_isect_emit", means2d, radii, depths, conics, opacities, image_ids,
+             cum, rows, n_per, I, tile_size, tile_width, tile_height, isect_ids, flatten_ids)
     if st.sort:
         isect_ids, flatten_ids = _sort_isects(isect_ids, flatten_ids, I, tile_width, tile_height, 32 + tile_bits + image_bits)
     return tiles_per_gauss, isect_ids, flatten_ids
@@ -631,11 +629,10 @@ def _sort_isects(isect_ids, flatten_ids, I, tw, th, key_bits):
     n, dev = isect_ids.numel(), isect_ids.device
     keys_alt, vals_alt = torch.empty_like(isect_ids), torch.empty_like(flatten_ids)
     if _cabi.tile_sort_supported(I, tw, th):
-        ws = torch.empty(_cabi.tile_sort_workspace_bytes(n, I, tw, th), device=dev, dtype=torch.uint8)
-        call("gsx_isect_tile_sort", ptr(isect_ids), ptr(flatten_ids), n, I, tw, th, ptr(keys_alt), ptr(vals_alt), ptr(ws),
-             ws.numel())
+        ws = torch.empty(_cabi.query("gsx_isect_tile_sort_workspace_bytes", n, I, tw, th), device=dev, dtype=torch.uint8)
+        call("gsx_isect_tile_sort", isect_ids, flatten_ids, n, I, tw, th, keys_alt, vals_alt, ws, ws.numel())
         return keys_alt, vals_alt
-    ws = torch.empty(_cabi.sort_workspace_bytes(n), device=dev, dtype=torch.uint8)
+    ws = torch.empty(_cabi.query("gsx_sort_pairs_workspace_bytes", n), device=dev, dtype=torch.uint8)
     if _cabi.sort_pairs(isect_ids, flatten_ids, keys_alt, vals_alt, n, key_bits, ws):
         return keys_alt, vals_alt
     return isect_ids, flatten_ids
@@ -656,7 +653,7 @@ def _lidar_tiling_args(lidar, dev):
         raise RuntimeError("lidar tiling: cdf_elevation [R + 1] and cdf_dense_ray_mask [R + 1, A + 1] expected")
     return ((float(lidar.fov_horiz_rad.start), float(lidar.fov_horiz_rad.span), float(lidar.fov_vert_rad.start),
              float(lidar.fov_vert_rad.span), int(lidar.spinning_direction), int(lidar.n_bins_azimuth), int(lidar.n_bins_elevation),
-             int(raycdf.shape[1] - 1), int(raycdf.shape[0] - 1), ptr(cdf_el), ptr(raycdf)), (cdf_el, raycdf))
+             int(raycdf.shape[1] - 1), int(raycdf.shape[0] - 1), cdf_el, raycdf), (cdf_el, raycdf))
 
 
 @_op("intersect_tile_lidar")
@@ -701,7 +698,7 @@ def intersect_tile_lidar(lidar, means2d, radii, depths, image_ids, gaussian_ids,
     radii = radii.contiguous()
     if radii.dtype not in (torch.int32, torch.float32):
         radii = radii.to(torch.float32) if radii.is_floating_point() else radii.to(torch.int32)
-    r_i, r_f = (ptr(radii), None) if radii.dtype == torch.int32 else (None, ptr(radii))
+    r_i, r_f = (radii, None) if radii.dtype == torch.int32 else (None, radii)
     rows = depths.numel()
     tiles_per_gauss = torch.empty(depths.shape, device=dev, dtype=torch.int32)
     empty = (tiles_per_gauss, torch.empty(0, device=dev, dtype=torch.int64), torch.empty(0, device=dev, dtype=torch.int32))
@@ -709,7 +706,7 @@ def intersect_tile_lidar(lidar, means2d, radii, depths, image_ids, gaussian_ids,
         return empty
     targs, _keep = _lidar_tiling_args(lidar, dev)
     n_per_arg = max(int(n_per), 1)
-    call("gsx_isect_lidar_count", ptr(means2d), r_i, r_f, rows, n_per_arg, *targs, ptr(tiles_per_gauss))
+    call("gsx_isect_lidar_count", means2d, r_i, r_f, rows, n_per_arg, *targs, tiles_per_gauss)
     cum = torch.cumsum(tiles_per_gauss.reshape(-1), 0, dtype=torch.int64)
     n_isects = int(cum[-1].item())  # host sync: exact-length outputs, like the reference (Intersect.cpp:470-480)
     if n_isects >= 2**31:
@@ -719,8 +716,7 @@ def intersect_tile_lidar(lidar, means2d, radii, depths, image_ids, gaussian_ids,
     isect_ids = torch.empty(n_isects, device=dev, dtype=torch.int64)
     flatten_ids = torch.empty(n_isects, device=dev, dtype=torch.int32)
     img = image_ids.contiguous().to(torch.int64) if packed else None
-    call("gsx_isect_lidar_emit", ptr(means2d), r_i, r_f, ptr(depths), ptr(img), ptr(cum), rows, n_per_arg, I, *targs,
-         ptr(isect_ids), ptr(flatten_ids))
+    call("gsx_isect_lidar_emit", means2d, r_i, r_f, depths, img, cum, rows, n_per_arg, I, *targs, isect_ids, flatten_ids)
     if sort:
         isect_ids, flatten_ids = _sort_isects(isect_ids, flatten_ids, I, int(lidar.n_bins_azimuth), int(lidar.n_bins_elevation),
                                               32 + tile_bits + image_bits)
@@ -773,18 +769,18 @@ def projection_ewa_3dgs_fused_bwd(means, covars, quats, scales, viewmats, Ks, im
     v_viewmats = torch.zeros_like(viewmats) if viewmats_requires_grad else None
     v_means2d, m2_stride = _row_view(v_means2d, 2)
     v_conics, con_stride = _row_view(v_conics, 3)
-    head = (ptr(means), ptr(covars), ptr(None if covars is not None else quats),
-            ptr(None if covars is not None else scales), ptr(viewmats), ptr(Ks), B, C, N, image_width, image_height,
-            eps2d, int(camera_model), ptr(radii.contiguous()), ptr(conics.contiguous()), ptr(_c(compensations)),
-            ptr_strided(v_means2d), m2_stride, ptr(_c(v_depths)), ptr_strided(v_conics), con_stride,
-            ptr(_c(v_compensations)))
+    head = (means, covars, None if covars is not None else quats,
+            None if covars is not None else scales, viewmats, Ks, B, C, N, image_width, image_height,
+            eps2d, int(camera_model), radii.contiguous(), conics.contiguous(), _c(compensations),
+            strided(v_means2d), m2_stride, _c(v_depths), strided(v_conics), con_stride,
+            _c(v_compensations))
     if _v_view_opacities is not None:
         v_view, opac_stride = _elem_view(_v_view_opacities)
         v_opacities = torch.empty(tuple(batch_dims) + (N,), device=means.device, dtype=means.dtype)
-        call("gsx_project_ewa_bwd_opac", *head, ptr_strided(v_view), opac_stride, ptr(v_means), ptr(v_covars), ptr(v_quats),
-             ptr(v_scales), ptr(v_viewmats), ptr(v_opacities))
+        call("gsx_project_ewa_bwd_opac", *head, strided(v_view), opac_stride, v_means, v_covars, v_quats,
+             v_scales, v_viewmats, v_opacities)
         return v_means, v_covars, v_quats, v_scales, v_viewmats, v_opacities
-    call("gsx_project_ewa_bwd", *head, ptr(v_means), ptr(v_covars), ptr(v_quats), ptr(v_scales), ptr(v_viewmats))
+    call("gsx_project_ewa_bwd", *head, v_means, v_covars, v_quats, v_scales, v_viewmats)
     return v_means, v_covars, v_quats, v_scales, v_viewmats
 
 
@@ -803,12 +799,12 @@ def projection_ewa_3dgs_packed_bwd(means, covars, quats, scales, viewmats, Ks, i
     v_viewmats = torch.zeros_like(viewmats) if viewmats_requires_grad else None
     v_means2d, m2_stride = _row_view(v_means2d, 2)
     v_conics, con_stride = _row_view(v_conics, 3)
-    head = (ptr(means), ptr(covars), ptr(None if covars is not None else quats),
-            ptr(None if covars is not None else scales), ptr(viewmats), ptr(Ks), B, C, N, image_width, image_height,
-            eps2d, int(camera_model), nnz, ptr(batch_ids.contiguous()), ptr(camera_ids.contiguous()),
-            ptr(gaussian_ids.contiguous()), ptr(conics.contiguous()), ptr(_c(compensations)),
-            ptr_strided(v_means2d), m2_stride, ptr(_c(v_depths)), ptr_strided(v_conics), con_stride,
-            ptr(_c(v_compensations)))
+    head = (means, covars, None if covars is not None else quats,
+            None if covars is not None else scales, viewmats, Ks, B, C, N, image_width, image_height,
+            eps2d, int(camera_model), nnz, batch_ids.contiguous(), camera_ids.contiguous(),
+            gaussian_ids.contiguous(), conics.contiguous(), _c(compensations),
+            strided(v_means2d), m2_stride, _c(v_depths), strided(v_conics), con_stride,
+            _c(v_compensations))
     def scatter_opacities():  # where no Gaussian-major kernel runs: what autograd does for opacities[ids] (an index_add)
         flat = torch.zeros(B * N, device=means.device, dtype=means.dtype)
         flat.index_add_(0, batch_ids * N + gaussian_ids if B > 1 else gaussian_ids, _v_view_opacities.reshape(-1))
@@ -826,8 +822,7 @@ def projection_ewa_3dgs_packed_bwd(means, covars, quats, scales, viewmats, Ks, i
         r_covars = rows(6) if covars is not None else None
         r_quats = rows(4) if covars is None else None
         r_scales = rows(3) if covars is None else None
-        call("gsx_project_ewa_packed_bwd_rows", *head, ptr(r_means), ptr(r_covars), ptr(r_quats), ptr(r_scales),
-             ptr(v_viewmats))
+        call("gsx_project_ewa_packed_bwd_rows", *head, r_means, r_covars, r_quats, r_scales, v_viewmats)
         flat = len(batch_dims) == 0
         indices = gaussian_ids.unsqueeze(0) if flat else torch.stack([batch_ids, gaussian_ids])
         coalesced = B * C == 1
@@ -862,11 +857,10 @@ def projection_ewa_3dgs_packed_bwd(means, covars, quats, scales, viewmats, Ks, i
         v_view, opac_stride = _elem_view(_v_view_opacities)
         # [..., N]: written once per Gaussian through the row map, accumulated into zeros without one
         v_opacities = (torch.empty if row_map is not None else torch.zeros)(tuple(batch_dims) + (N,), device=means.device, dtype=means.dtype)
-        call("gsx_project_ewa_packed_bwd_opac", *head, ptr_strided(v_view), opac_stride, ptr(row_map), ptr(v_means), ptr(v_covars),
-             ptr(v_quats), ptr(v_scales), ptr(v_viewmats), ptr(v_opacities))
+        call("gsx_project_ewa_packed_bwd_opac", *head, strided(v_view), opac_stride, row_map, v_means, v_covars,
+             v_quats, v_scales, v_viewmats, v_opacities)
     else:
-        call("gsx_project_ewa_packed_bwd", *head, ptr(row_map), ptr(v_means), ptr(v_covars), ptr(v_quats), ptr(v_scales),
-             ptr(v_viewmats))
+        call("gsx_project_ewa_packed_bwd", *head, row_map, v_means, v_covars, v_quats, v_scales, v_viewmats)
     # the last consumer of a step's row map (autograd runs the SH backward, created later, first): drop it here, and with it
     # the references that keep the step's id tensors alive - a stage-level caller has no next rasterization() to do that
     clear_row_map_cache()
@@ -929,22 +923,20 @@ def rasterize_to_pixels_3dgs_bwd(means2d, conics, colors, opacities, backgrounds
         v_render_colors = v_render_colors.contiguous()
         vrc_strides = (-1, 1)
     if segmented:
-        ws = torch.empty(_cabi._lib.gsx_raster3d_bwd_seg_workspace_bytes(flatten_ids.numel(), I, tw, th, D, SEG_LEN),
+        ws = torch.empty(_cabi.query("gsx_raster3d_bwd_seg_workspace_bytes", flatten_ids.numel(), I, tw, th, D, SEG_LEN),
                          device=means2d.device, dtype=torch.uint8)
         fws = _lookup_seg_workspace(last_ids, flatten_ids.numel(), D, as_received)  # the forward call's workspace, if still around
-        call("gsx_raster3d_bwd_seg_reuse", ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds), ptr(masks),
-             ptr(tile_offsets.contiguous()), ptr(flatten_ids.contiguous()), ptr(render_alphas.contiguous()),
-             ptr(last_ids.contiguous()), ptr(v_render_colors), ptr(v_render_alphas), I, flatten_ids.numel(), D,
-             image_width, image_height, tile_size, tw, th, ptr(rows), geo + D, SEG_LEN, ptr(fws),
-             0 if fws is None else fws.numel(), ptr(ws), ws.numel())
+        call("gsx_raster3d_bwd_seg_reuse", means2d, conics, colors, opacities, backgrounds, masks, tile_offsets.contiguous(),
+             flatten_ids.contiguous(), render_alphas.contiguous(), last_ids.contiguous(), v_render_colors, v_render_alphas, I,
+             flatten_ids.numel(), D, image_width, image_height, tile_size, tw, th, rows, geo + D, SEG_LEN, fws,
+             0 if fws is None else fws.numel(), ws, ws.numel())
     else:
         # workspace for the longest-first tile order of the launch (csrc/raster3d_bwd.hip: "longest tiles first")
-        ws = torch.empty(_cabi._lib.gsx_raster3d_bwd_workspace_bytes(I, tw, th), device=means2d.device, dtype=torch.uint8)
-        call("gsx_raster3d_bwd_fill", ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds), ptr(masks),
-             ptr(tile_offsets.contiguous()), ptr(flatten_ids.contiguous()), ptr(render_alphas.contiguous()),
-             ptr(last_ids.contiguous()), ptr_strided(v_render_colors), ptr(v_render_alphas), I, flatten_ids.numel(), D,
-             image_width, image_height, tile_size, tw, th, int(bool(absgrad)), ptr(rows), geo + D, R, vrc_strides[0],
-             vrc_strides[1], ptr(ws), ws.numel())
+        ws = torch.empty(_cabi.query("gsx_raster3d_bwd_workspace_bytes", I, tw, th), device=means2d.device, dtype=torch.uint8)
+        call("gsx_raster3d_bwd_fill", means2d, conics, colors, opacities, backgrounds, masks, tile_offsets.contiguous(),
+             flatten_ids.contiguous(), render_alphas.contiguous(), last_ids.contiguous(), strided(v_render_colors),
+             v_render_alphas, I, flatten_ids.numel(), D, image_width, image_height, tile_size, tw, th, int(bool(absgrad)), rows,
+             geo + D, R, vrc_strides[0], vrc_strides[1], ws, ws.numel())
     v_means2d, v_conics = rows[:, 0:2].view(means2d.shape), rows[:, 2:5].view(conics.shape)
     v_opacities, v_colors = rows[:, 5].view(opacities.shape), rows[:, geo:].view(colors.shape)
     v_abs = rows[:, 6:8].view(means2d.shape) if absgrad else None
@@ -1001,12 +993,12 @@ def _sh_band_fwd(degrees_to_use, first_band, means, viewmats, coeffs, masks, bat
     if packed:
         nnz = gaussian_ids.shape[0]
         colors = torch.empty((nnz, 3), device=means.device, dtype=means.dtype)
-        call("gsx_sh_band_fwd", degrees_to_use, first_band, _BAND_DTYPES[coeffs.dtype], ptr(means), ptr(viewmats), ptr(coeffs),
-             ptr(masks), ptr(_c(batch_ids)), ptr(_c(camera_ids)), ptr(_c(gaussian_ids)), B, C, N, nnz, K, ptr(colors))
+        call("gsx_sh_band_fwd", degrees_to_use, first_band, _BAND_DTYPES[coeffs.dtype], means, viewmats, coeffs,
+             masks, _c(batch_ids), _c(camera_ids), _c(gaussian_ids), B, C, N, nnz, K, colors)
     else:
         colors = torch.empty(viewmats.shape[:-2] + (N, 3), device=means.device, dtype=means.dtype)
-        call("gsx_sh_band_fwd", degrees_to_use, first_band, _BAND_DTYPES[coeffs.dtype], ptr(means), ptr(viewmats), ptr(coeffs),
-             ptr(masks), None, None, None, B, C, N, -1, K, ptr(colors))
+        call("gsx_sh_band_fwd", degrees_to_use, first_band, _BAND_DTYPES[coeffs.dtype], means, viewmats, coeffs,
+             masks, None, None, None, B, C, N, -1, K, colors)
     return colors
 
 
@@ -1025,8 +1017,8 @@ def _sh_band_bwd(degrees_to_use, first_band, means, viewmats, coeffs, masks, bat
     v_dirs = None
     if compute_v_viewmats:
         v_dirs = torch.zeros(((nnz if packed else B * C * N), 3), device=means.device, dtype=means.dtype)
-    call("gsx_sh_band_bwd", degrees_to_use, first_band, _BAND_DTYPES[coeffs.dtype], ptr(means), ptr(viewmats), ptr(coeffs),
-         ptr(masks), B, C, N, nnz, K, ptr(v_colors.contiguous()), ptr(row_map), ptr(v_coeffs), ptr(v_means), ptr(v_dirs))
+    call("gsx_sh_band_bwd", degrees_to_use, first_band, _BAND_DTYPES[coeffs.dtype], means, viewmats, coeffs,
+         masks, B, C, N, nnz, K, v_colors.contiguous(), row_map, v_coeffs, v_means, v_dirs)
     v_viewmats = None
     if compute_v_viewmats:
         if packed:
@@ -1111,8 +1103,7 @@ def projection_ewa_simple(means, covars, Ks, width, height, camera_model):
     rows = means.numel() // 3
     means2d = torch.empty(means.shape[:-1] + (2,), device=means.device, dtype=means.dtype)
     covars2d = torch.empty(means.shape[:-1] + (2, 2), device=means.device, dtype=means.dtype)
-    call("gsx_project_simple_fwd", ptr(means), ptr(covars), ptr(Ks), rows, N, width, height, int(camera_model),
-         ptr(means2d), ptr(covars2d))
+    call("gsx_project_simple_fwd", means, covars, Ks, rows, N, width, height, int(camera_model), means2d, covars2d)
     return means2d, covars2d
 
 
@@ -1122,8 +1113,8 @@ def projection_ewa_simple_bwd(means, covars, Ks, width, height, camera_model, v_
     N = means.shape[-2]
     rows = means.numel() // 3
     v_means, v_covars = torch.empty_like(means), torch.empty_like(covars)
-    call("gsx_project_simple_bwd", ptr(means), ptr(covars), ptr(Ks), rows, N, width, height, int(camera_model),
-         ptr(v_means2d.contiguous()), ptr(v_covars2d.contiguous()), ptr(v_means), ptr(v_covars))
+    call("gsx_project_simple_bwd", means, covars, Ks, rows, N, width, height, int(camera_model),
+         v_means2d.contiguous(), v_covars2d.contiguous(), v_means, v_covars)
     return v_means, v_covars
 
 
@@ -1141,20 +1132,20 @@ def _raster_indices(mode, range_start, range_end, transmittances, means2d, geom,
                          f"{tuple(transmittances.shape)}")
     th, tw = tile_offsets.shape[-2], tile_offsets.shape[-1]
     dev = means2d.device
-    args = (int(mode), int(range_start), int(range_end), ptr(transmittances.contiguous()), ptr(means2d.contiguous()),
-            ptr(geom.contiguous()), ptr(opacities.contiguous()), ptr(tile_offsets.contiguous()),
-            ptr(flatten_ids.contiguous()), I, N, flatten_ids.numel(), image_width, image_height, tile_size, tw, th)
+    args = (int(mode), int(range_start), int(range_end), transmittances.contiguous(), means2d.contiguous(),
+            geom.contiguous(), opacities.contiguous(), tile_offsets.contiguous(),
+            flatten_ids.contiguous(), I, N, flatten_ids.numel(), image_width, image_height, tile_size, tw, th)
     cnts = torch.zeros(I * image_height * image_width, device=dev, dtype=torch.int32)
     n_elems = 0
     if cnts.numel() > 0 and flatten_ids.numel() > 0:
-        call("gsx_raster_indices", *args, None, ptr(cnts), None, None)
+        call("gsx_raster_indices", *args, None, cnts, None, None)
         cum = torch.cumsum(cnts, 0, dtype=torch.int32)
         n_elems = int(cum[-1].item())
         starts = (cum - cnts).contiguous()
     gaussian_ids = torch.empty(n_elems, device=dev, dtype=torch.int64)
     combined = torch.empty(n_elems, device=dev, dtype=torch.int64)
     if n_elems:
-        call("gsx_raster_indices", *args, ptr(starts), None, ptr(gaussian_ids), ptr(combined))
+        call("gsx_raster_indices", *args, starts, None, gaussian_ids, combined)
     pix_per_image = image_height * image_width
     return gaussian_ids, torch.remainder(combined, pix_per_image), torch.div(combined, pix_per_image,
                                                                             rounding_mode="floor")
@@ -1200,16 +1191,16 @@ def projection_2dgs_fused_bwd(means, quats, scales, viewmats, Ks, image_width, i
     # the depth cotangent is read in place when it is one column of the gradient rows (the slice autograd cuts out of the
     # colour cotangent of a depth render mode), like the three above
     v_dep, dep_stride = (None, 1) if v_depths is None else _elem_view(v_depths)
-    head = (ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), B, C, N,
-            ptr(radii.contiguous()), ptr(ray_transforms.contiguous()), ptr_strided(v_means2d),
-            None if v_dep is None else ptr_strided(v_dep), ptr_strided(v_rt), ptr_strided(v_normals), vstride, int(dep_stride))
+    head = (means, quats, scales, viewmats, Ks, B, C, N,
+            radii.contiguous(), ray_transforms.contiguous(), strided(v_means2d),
+            None if v_dep is None else strided(v_dep), strided(v_rt), strided(v_normals), vstride, int(dep_stride))
     if _v_view_opacities is not None:
         v_view, opac_stride = _elem_view(_v_view_opacities)
         v_opacities = torch.empty(tuple(batch_dims) + (N,), device=means.device, dtype=means.dtype)
-        call("gsx_project_2dgs_bwd_opac", *head, ptr_strided(v_view), opac_stride, ptr(v_means), ptr(v_quats), ptr(v_scales),
-             ptr(v_viewmats), ptr(v_opacities))
+        call("gsx_project_2dgs_bwd_opac", *head, strided(v_view), opac_stride, v_means, v_quats, v_scales,
+             v_viewmats, v_opacities)
         return v_means, v_quats, v_scales, v_viewmats, v_opacities
-    call("gsx_project_2dgs_bwd", *head, ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_viewmats))
+    call("gsx_project_2dgs_bwd", *head, v_means, v_quats, v_scales, v_viewmats)
     return v_means, v_quats, v_scales, v_viewmats
 
 
@@ -1221,12 +1212,12 @@ def projection_2dgs_packed(means, quats, scales, viewmats, Ks, image_width, imag
     means, quats, scales, viewmats, Ks = (t.contiguous() for t in (means, quats, scales, viewmats, Ks))
     dev, dt = means.device, means.dtype
     total = B * C * N
-    common = (ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), B, C, N, image_width, image_height,
+    common = (means, quats, scales, viewmats, Ks, B, C, N, image_width, image_height,
               near_plane, far_plane, radius_clip)
     nnz, cum = 0, None
     if total > 0:
         visible = torch.empty(total, device=dev, dtype=torch.int32)
-        call("gsx_project_2dgs_packed_count", *common, ptr(visible))
+        call("gsx_project_2dgs_packed_count", *common, visible)
         cum = _scan_i32(visible)
         nnz = int(cum[-1].item())  # host sync: exact-length COO outputs, as the reference
     batch_ids = torch.empty(nnz, device=dev, dtype=torch.int64)
@@ -1239,8 +1230,8 @@ def projection_2dgs_packed(means, quats, scales, viewmats, Ks, image_width, imag
     ray_transforms = torch.empty((nnz, 3, 3), device=dev, dtype=dt)
     normals = torch.empty((nnz, 3), device=dev, dtype=dt)
     if total > 0:
-        call("gsx_project_2dgs_packed_write", *common, ptr(cum), nnz, ptr(batch_ids), ptr(camera_ids),
-             ptr(gaussian_ids), ptr(indptr), ptr(radii), ptr(means2d), ptr(depths), ptr(ray_transforms), ptr(normals))
+        call("gsx_project_2dgs_packed_write", *common, cum, nnz, batch_ids, camera_ids,
+             gaussian_ids, indptr, radii, means2d, depths, ray_transforms, normals)
     return batch_ids, camera_ids, gaussian_ids, indptr, radii, means2d, depths, ray_transforms, normals
 
 
@@ -1254,15 +1245,15 @@ def projection_2dgs_packed_bwd(means, quats, scales, viewmats, Ks, image_width, 
     v_viewmats = torch.zeros_like(viewmats) if viewmats_requires_grad else None
     (v_means2d, v_rt, v_normals), vstride = _common_row_views(
         (v_means2d, v_ray_transforms.reshape(v_ray_transforms.shape[:-2] + (9,)), v_normals), (2, 9, 3))
-    head = (ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), B, C, N, nnz,
-            ptr(batch_ids.contiguous()), ptr(camera_ids.contiguous()), ptr(gaussian_ids.contiguous()),
-            ptr(ray_transforms.contiguous()), ptr_strided(v_means2d), ptr(_c(v_depths)), ptr_strided(v_rt),
-            ptr_strided(v_normals), vstride)
+    head = (means, quats, scales, viewmats, Ks, B, C, N, nnz,
+            batch_ids.contiguous(), camera_ids.contiguous(), gaussian_ids.contiguous(),
+            ray_transforms.contiguous(), strided(v_means2d), _c(v_depths), strided(v_rt),
+            strided(v_normals), vstride)
     if sparse_grad and len(batch_dims) == 0:
         # COO gradients as the reference builds them (Projection.cpp:1780-1863): [nnz, .] rows from the kernel, indices =
         # gaussian_ids, coalesced iff a single image; no dense [N, .] tensor, nothing read back
         r_means, r_quats, r_scales = (torch.empty((nnz, w), device=means.device, dtype=means.dtype) for w in (3, 4, 3))
-        call("gsx_project_2dgs_packed_bwd_rows", *head, ptr(r_means), ptr(r_quats), ptr(r_scales), ptr(v_viewmats))
+        call("gsx_project_2dgs_packed_bwd_rows", *head, r_means, r_quats, r_scales, v_viewmats)
         indices = gaussian_ids.unsqueeze(0)
 
         def coo(vals, like):
@@ -1271,7 +1262,7 @@ def projection_2dgs_packed_bwd(means, quats, scales, viewmats, Ks, image_width, 
         clear_row_map_cache()  # a packed 2DGS step's SH backward leaves its map; nothing after this op walks it
         return coo(r_means, means), coo(r_quats, quats), coo(r_scales, scales), v_viewmats
     v_means, v_quats, v_scales = torch.zeros_like(means), torch.zeros_like(quats), torch.zeros_like(scales)
-    call("gsx_project_2dgs_packed_bwd", *head, ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_viewmats))
+    call("gsx_project_2dgs_packed_bwd", *head, v_means, v_quats, v_scales, v_viewmats)
     clear_row_map_cache()
     return v_means, v_quats, v_scales, v_viewmats
 
@@ -1297,13 +1288,12 @@ def rasterize_to_pixels_2dgs_bwd(means2d, ray_transforms, colors, opacities, nor
     geo = 19 if absgrad else 17
     rows = torch.empty((R, geo + D), device=means2d.device, dtype=means2d.dtype)
     # workspace for the longest-first tile order of the launch (csrc/tile_order.hip)
-    ws = torch.empty(_cabi._lib.gsx_raster3d_bwd_workspace_bytes(I, tw, th), device=means2d.device, dtype=torch.uint8)
-    call("gsx_raster2d_bwd_fill", ptr(means2d), ptr(ray_transforms), ptr(colors), ptr(opacities), ptr(normals),
-         ptr(backgrounds), ptr(masks), ptr(tile_offsets.contiguous()), ptr(flatten_ids.contiguous()),
-         ptr(render_colors.contiguous()), ptr(render_alphas.contiguous()), ptr(last_ids.contiguous()),
-         ptr(median_ids.contiguous()), ptr(v_render_colors), ptr(_c(v_render_alphas)), ptr(_c(v_render_normals)),
-         ptr(_c(v_render_distort)), ptr(_c(v_render_median)), I, flatten_ids.numel(), D, image_width,
-         image_height, tile_size, tw, th, int(bool(absgrad)), ptr(rows), geo + D, R, ptr(ws), ws.numel())
+    ws = torch.empty(_cabi.query("gsx_raster3d_bwd_workspace_bytes", I, tw, th), device=means2d.device, dtype=torch.uint8)
+    call("gsx_raster2d_bwd_fill", means2d, ray_transforms, colors, opacities, normals, backgrounds, masks,
+         tile_offsets.contiguous(), flatten_ids.contiguous(), render_colors.contiguous(), render_alphas.contiguous(),
+         last_ids.contiguous(), median_ids.contiguous(), v_render_colors, _c(v_render_alphas), _c(v_render_normals),
+         _c(v_render_distort), _c(v_render_median), I, flatten_ids.numel(), D, image_width, image_height, tile_size, tw, th,
+         int(bool(absgrad)), rows, geo + D, R, ws, ws.numel())
     v_means2d, v_opacities = rows[:, 0:2].view(means2d.shape), rows[:, 2].view(opacities.shape)
     v_densify, v_normals = rows[:, 3:5].view(means2d.shape), rows[:, 5:8].view(normals.shape)
     v_rt = rows[:, 8:17].view(ray_transforms.shape)
@@ -1326,8 +1316,8 @@ def _query_common(means2d, conics, opacities, tile_offsets, flatten_ids, image_w
         raise ValueError("tile grid does not cover the image")
     packed = means2d.dim() == 2
     n_per = 0 if packed else means2d.shape[-2]
-    args = (ptr(means2d.contiguous()), ptr(conics.contiguous()), ptr(opacities.contiguous()),
-            ptr(tile_offsets.contiguous()), ptr(flatten_ids.contiguous()), I, flatten_ids.numel(), n_per, image_width,
+    args = (means2d.contiguous(), conics.contiguous(), opacities.contiguous(),
+            tile_offsets.contiguous(), flatten_ids.contiguous(), I, flatten_ids.numel(), n_per, image_width,
             image_height, tile_size, tw, th)
     return image_dims + (image_height, image_width), args
 
@@ -1338,7 +1328,7 @@ def rasterize_num_contributing_gaussians(means2d, conics, opacities, tile_offset
     hw, args = _query_common(means2d, conics, opacities, tile_offsets, flatten_ids, image_width, image_height, tile_size)
     counts = torch.empty(hw, device=means2d.device, dtype=torch.int32)
     alphas = torch.empty(hw, device=means2d.device, dtype=means2d.dtype)
-    call("gsx_raster3d_num_contributing", *args, ptr(counts), ptr(alphas))
+    call("gsx_raster3d_num_contributing", *args, counts, alphas)
     return counts, alphas
 
 
@@ -1350,7 +1340,7 @@ def rasterize_contributing_gaussian_ids(means2d, conics, opacities, tile_offsets
     kmax = int(num_contributing_gaussians.max().item()) if num_contributing_gaussians.numel() > 0 else 0
     ids = torch.full(hw + (kmax,), -1, device=means2d.device, dtype=torch.int32)
     weights = torch.zeros(hw + (kmax,), device=means2d.device, dtype=means2d.dtype)
-    call("gsx_raster3d_contributing_ids", *args, kmax, ptr(ids), ptr(weights))
+    call("gsx_raster3d_contributing_ids", *args, kmax, ids, weights)
     return ids, weights
 
 
@@ -1362,7 +1352,7 @@ def rasterize_top_contributing_gaussian_ids(means2d, conics, opacities, tile_off
         raise ValueError("num_depth_samples must be >= 0")
     ids = torch.empty(hw + (num_depth_samples,), device=means2d.device, dtype=torch.int32)
     weights = torch.empty(hw + (num_depth_samples,), device=means2d.device, dtype=means2d.dtype)
-    call("gsx_raster3d_top_contributing", *args, num_depth_samples, ptr(ids), ptr(weights))
+    call("gsx_raster3d_top_contributing", *args, num_depth_samples, ids, weights)
     return ids, weights
 
 
@@ -1471,8 +1461,8 @@ def _sparse_layout_args(active_tiles, tile_offsets, flatten_ids, tile_pixel_mask
     if tile_offsets.shape[0] != AT + 1:
         raise ValueError("tile_offsets must be [num_active_tiles + 1]")
     words = tile_pixel_mask.shape[1] if tile_pixel_mask.dim() == 2 else (tile_size * tile_size + 63) // 64
-    return (ptr(active_tiles.contiguous()), ptr(tile_offsets.contiguous()), ptr(flatten_ids.contiguous()),
-            ptr(tile_pixel_mask.contiguous()), ptr(tile_pixel_cumsum.contiguous()), ptr(pixel_map.contiguous()), AT, words)
+    return (active_tiles.contiguous(), tile_offsets.contiguous(), flatten_ids.contiguous(),
+            tile_pixel_mask.contiguous(), tile_pixel_cumsum.contiguous(), pixel_map.contiguous(), AT, words)
 
 
 @_op("rasterize_to_pixels_sparse")
@@ -1494,9 +1484,9 @@ def rasterize_to_pixels_sparse(means2d, conics, colors, opacities, backgrounds, 
     alphas = torch.empty((P, 1), device=dev, dtype=dt)
     last_ids = torch.empty((P,), device=dev, dtype=torch.int32)
     a_t, t_off, f_ids, p_mask, p_cum, p_map, AT, words = layout
-    call("gsx_raster3d_sparse_fwd", ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds), ptr(masks),
+    call("gsx_raster3d_sparse_fwd", means2d, conics, colors, opacities, backgrounds, masks,
          a_t, t_off, f_ids, p_mask, p_cum, p_map, AT, words, 0, flatten_ids.numel(), D, image_width, image_height,
-         tile_size, tile_width, tile_height, ptr(renders), ptr(alphas), ptr(last_ids))
+         tile_size, tile_width, tile_height, renders, alphas, last_ids)
     holder = torch.zeros_like(means2d) if absgrad else torch.empty(0, device=dev, dtype=dt)
     return renders, alphas, holder, last_ids
 
@@ -1516,10 +1506,10 @@ def rasterize_to_pixels_sparse_bwd(means2d, conics, colors, opacities, backgroun
     geo = 8 if absgrad else 6
     rows = torch.zeros((R, geo + D), device=means2d.device, dtype=means2d.dtype)  # AoS rows, see rasterize_to_pixels_3dgs_bwd
     a_t, t_off, f_ids, p_mask, p_cum, p_map, AT, words = layout
-    call("gsx_raster3d_sparse_bwd", ptr(means2d), ptr(conics), ptr(colors), ptr(opacities), ptr(backgrounds), ptr(masks),
-         a_t, t_off, f_ids, p_mask, p_cum, p_map, AT, words, ptr(render_alphas.contiguous()), ptr(last_ids.contiguous()),
-         ptr(v_render_colors), ptr(v_render_alphas), 0, flatten_ids.numel(), D, image_width, image_height, tile_size,
-         tile_width, tile_height, int(bool(absgrad)), ptr(rows), geo + D)
+    call("gsx_raster3d_sparse_bwd", means2d, conics, colors, opacities, backgrounds, masks,
+         a_t, t_off, f_ids, p_mask, p_cum, p_map, AT, words, render_alphas.contiguous(), last_ids.contiguous(),
+         v_render_colors, v_render_alphas, 0, flatten_ids.numel(), D, image_width, image_height, tile_size,
+         tile_width, tile_height, int(bool(absgrad)), rows, geo + D)
     v_means2d, v_conics = rows[:, 0:2].view(means2d.shape), rows[:, 2:5].view(conics.shape)
     v_opacities, v_colors = rows[:, 5].view(opacities.shape), rows[:, geo:].view(colors.shape)
     v_abs = rows[:, 6:8].view(means2d.shape) if absgrad else None
@@ -1537,7 +1527,7 @@ def _sparse_query_common(means2d, conics, opacities, image_width, image_height, 
     a_t, t_off, f_ids, p_mask, p_cum, p_map, AT, words = _sparse_layout_args(
         active_tiles, tile_offsets, flatten_ids, tile_pixel_mask, tile_pixel_cumsum, pixel_map, tile_size)
     n_per = 0 if means2d.dim() == 2 else means2d.shape[-2]
-    return (ptr(means2d.contiguous()), ptr(conics.contiguous()), ptr(opacities.contiguous()), a_t, t_off, f_ids, p_mask,
+    return (means2d.contiguous(), conics.contiguous(), opacities.contiguous(), a_t, t_off, f_ids, p_mask,
             p_cum, p_map, AT, words, 0, flatten_ids.numel(), n_per, image_width, image_height, tile_size, tile_width,
             tile_height)
 
@@ -1551,7 +1541,7 @@ def rasterize_num_contributing_gaussians_sparse(means2d, conics, opacities, imag
     P = pixel_map.shape[0]
     counts = torch.empty(P, device=means2d.device, dtype=torch.int32)
     alphas = torch.empty(P, device=means2d.device, dtype=means2d.dtype)
-    call("gsx_raster3d_sparse_num_contributing", *args, ptr(counts), ptr(alphas))
+    call("gsx_raster3d_sparse_num_contributing", *args, counts, alphas)
     return counts, alphas
 
 
@@ -1567,7 +1557,7 @@ def rasterize_contributing_gaussian_ids_sparse(means2d, conics, opacities, image
     kmax = int(num_contributing_gaussians.max().item()) if num_contributing_gaussians.numel() > 0 else 0
     ids = torch.full((P, kmax), -1, device=means2d.device, dtype=torch.int32)
     weights = torch.zeros((P, kmax), device=means2d.device, dtype=means2d.dtype)
-    call("gsx_raster3d_sparse_contributing_ids", *args, kmax, ptr(ids), ptr(weights))
+    call("gsx_raster3d_sparse_contributing_ids", *args, kmax, ids, weights)
     return ids, weights
 
 
@@ -1583,7 +1573,7 @@ def rasterize_top_contributing_gaussian_ids_sparse(means2d, conics, opacities, i
     P = pixel_map.shape[0]
     ids = torch.full((P, num_depth_samples), -1, device=means2d.device, dtype=torch.int32)
     weights = torch.zeros((P, num_depth_samples), device=means2d.device, dtype=means2d.dtype)
-    call("gsx_raster3d_sparse_top_contributing", *args, num_depth_samples, ptr(ids), ptr(weights))
+    call("gsx_raster3d_sparse_top_contributing", *args, num_depth_samples, ids, weights)
     return ids, weights
 
 
@@ -1602,7 +1592,7 @@ def adam(param, param_grad, exp_avg, exp_avg_sq, valid, lr, b1, b2, eps):
         if valid.dtype != torch.bool or valid.numel() != n_rows:
             raise ValueError("adam: valid must be a bool tensor with one entry per row of param")
         valid = valid.contiguous()
-    call("gsx_adam", ptr(param), ptr(param_grad.contiguous()), ptr(exp_avg), ptr(exp_avg_sq), ptr(valid), n_rows, width,
+    call("gsx_adam", param, param_grad.contiguous(), exp_avg, exp_avg_sq, valid, n_rows, width,
          float(lr), float(b1), float(b2), float(eps))
 
 
@@ -1615,8 +1605,7 @@ def relocation(opacities, scales, ratios, binoms, n_max, min_opacity=0.0):
     opacities, scales, binoms = opacities.contiguous(), scales.contiguous(), binoms.contiguous()
     ratios = ratios.to(torch.int32).contiguous()
     new_opacities, new_scales = torch.empty_like(opacities), torch.empty_like(scales)
-    call("gsx_relocation", ptr(opacities), ptr(scales), ptr(ratios), ptr(binoms), n, int(n_max), float(min_opacity),
-         ptr(new_opacities), ptr(new_scales))
+    call("gsx_relocation", opacities, scales, ratios, binoms, n, int(n_max), float(min_opacity), new_opacities, new_scales)
     return new_opacities, new_scales
 
 
@@ -1627,8 +1616,8 @@ def mcmc_perturb_positions(positions, quats, scales, opacities, noise, noise_sca
     if not positions.is_contiguous():
         raise ValueError("mcmc_perturb_positions: positions is updated in place and must be contiguous")
     n = positions.shape[0]
-    call("gsx_mcmc_perturb", ptr(positions), ptr(quats.contiguous()), ptr(scales.contiguous()),
-         ptr(opacities.reshape(-1).contiguous()), ptr(noise.contiguous()), n, float(noise_scale), float(t), float(k))
+    call("gsx_mcmc_perturb", positions, quats.contiguous(), scales.contiguous(),
+         opacities.reshape(-1).contiguous(), noise.contiguous(), n, float(noise_scale), float(t), float(k))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1664,10 +1653,9 @@ def assemble_proj_features_unpacked_fwd(degrees_to_use, B, C, N, Dc, E, color_po
             raise ValueError("relu_mask must be a contiguous bool [B, C, N, Dc] tensor")
         if color_post != 2:
             raise ValueError("relu_mask is only valid with color_post = 2 (shift + relu)")
-    call("gsx_assemble_features_fwd", int(degrees_to_use), B, C, N, coeffs.shape[1], Dc, E, int(color_post),
-         int(extra_post), int(has_depth), int(extra_has_c), ptr(means.contiguous()), ptr(viewmats.contiguous()),
-         ptr(coeffs.contiguous()), ptr(_c(extra)) if E > 0 else None, ptr(_c(depths)) if use_depths else None,
-         ptr(_c(masks)), ptr(out), ptr(relu_mask))
+    call("gsx_assemble_features_fwd", int(degrees_to_use), B, C, N, coeffs.shape[1], Dc, E, int(color_post), int(extra_post),
+         int(has_depth), int(extra_has_c), means.contiguous(), viewmats.contiguous(), coeffs.contiguous(),
+         _c(extra) if E > 0 else None, _c(depths) if use_depths else None, _c(masks), out, relu_mask)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1765,11 +1753,11 @@ def _projection_ut_lidar(means, quats, scales, opacities, viewmats0, viewmats1, 
     comps = torch.empty(batch + (C, N), device=dev, dtype=dt) if calc_compensations else None
     amap = _lidar_angle_map(lidar, dev) if rolling else None
     mh, mw = (int(amap.shape[0]), int(amap.shape[1])) if amap is not None else (0, 0)
-    call("gsx_project_ut_lidar_fwd", ptr(means.contiguous()), ptr(quats.contiguous()), ptr(scales.contiguous()),
-         ptr(_c(opacities)), ptr(viewmats0.contiguous()), ptr(_c(viewmats1)) if rolling else None, ptr(Ks.contiguous()),
-         *_lidar_fov_args(lidar), int(lidar.spinning_direction), ptr(amap), mh, mw, int(lidar.column_azimuths_rad.shape[0]), B, C,
+    call("gsx_project_ut_lidar_fwd", means.contiguous(), quats.contiguous(), scales.contiguous(),
+         _c(opacities), viewmats0.contiguous(), _c(viewmats1) if rolling else None, Ks.contiguous(),
+         *_lidar_fov_args(lidar), int(lidar.spinning_direction), amap, mh, mw, int(lidar.column_azimuths_rad.shape[0]), B, C,
          N, float(eps2d), float(near_plane), float(far_plane), float(radius_clip), int(rs_type), int(bool(global_z_order)), alpha,
-         beta, kappa, margin, int(all_valid), ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps))
+         beta, kappa, margin, int(all_valid), radii, means2d, depths, conics, comps)
     return radii, means2d, depths, conics, comps
 
 
@@ -1787,9 +1775,9 @@ def lidar_element_rays(viewmats: Tensor, viewmats_rs: Optional[Tensor], lidar, r
     amap = _lidar_angle_map(lidar, dev) if rolling else None
     mh, mw = (int(amap.shape[0]), int(amap.shape[1])) if amap is not None else (0, 0)
     rays = torch.empty(lead + (rows.shape[0], cols.shape[0], 6), device=dev, dtype=dt)
-    call("gsx_lidar_rays", ptr(viewmats.contiguous()), ptr(_c(viewmats_rs)) if rolling else None, ptr(rows), ptr(cols), ptr(offs),
+    call("gsx_lidar_rays", viewmats.contiguous(), _c(viewmats_rs) if rolling else None, rows, cols, offs,
          math.prod(lead), int(rows.shape[0]), int(cols.shape[0]), *_lidar_fov_args(lidar), float(lidar.fov_eps_rad),
-         int(lidar.spinning_direction), ptr(amap), mh, mw, int(rs_type), ptr(rays))
+         int(lidar.spinning_direction), amap, mh, mw, int(rs_type), rays)
     return rays
 
 
@@ -1902,14 +1890,14 @@ def projection_ut_3dgs_fused(means, quats, scales, opacities, viewmats0, viewmat
 
         if rolling and viewmats1.shape != viewmats0.shape:
             raise ValueError("viewmats_rs must match viewmats shape")
-        head = (ptr(means.contiguous()), ptr(quats.contiguous()), ptr(scales.contiguous()),
-                ptr(_c(opacities)), ptr(viewmats0.contiguous()), ptr(_c(viewmats1)) if rolling else None, ptr(Ks.contiguous()),
-                ptr(_c(radial_coeffs)), ptr(_c(tangential_coeffs)), ptr(_c(thin_prism_coeffs)), ptr(max_angle),
+        head = (means.contiguous(), quats.contiguous(), scales.contiguous(),
+                _c(opacities), viewmats0.contiguous(), _c(viewmats1) if rolling else None, Ks.contiguous(),
+                _c(radial_coeffs), _c(tangential_coeffs), _c(thin_prism_coeffs), max_angle,
                 ctypes.addressof(ftheta_rec) if ftheta_rec is not None else None)
         tail = (B, C, N, int(image_width), int(image_height),
                 float(eps2d), float(near_plane), float(far_plane), float(radius_clip), int(camera_model), int(rs_type),
-                int(bool(global_z_order)), alpha, beta, kappa, margin, int(all_valid), ptr(radii), ptr(means2d), ptr(depths),
-                ptr(conics), ptr(comps))
+                int(bool(global_z_order)), alpha, beta, kappa, margin, int(all_valid), radii, means2d, depths,
+                conics, comps)
         if external_distortion_params is not None:  # behind a windshield: sigma points go through the forward polynomials
             ext = _windshield_record(external_distortion_params)
             call("gsx_project_ut_ext_fwd", *head, ctypes.addressof(ext), *tail)
@@ -1919,17 +1907,15 @@ def projection_ut_3dgs_fused(means, quats, scales, opacities, viewmats0, viewmat
     if ftheta_rec is not None:
         import ctypes
 
-        call("gsx_project_ut_ftheta_fwd", ptr(means.contiguous()), ptr(quats.contiguous()), ptr(scales.contiguous()),
-             ptr(_c(opacities)), ptr(viewmats0.contiguous()), ptr(Ks.contiguous()), ctypes.addressof(ftheta_rec), B, C, N,
+        call("gsx_project_ut_ftheta_fwd", means.contiguous(), quats.contiguous(), scales.contiguous(),
+             _c(opacities), viewmats0.contiguous(), Ks.contiguous(), ctypes.addressof(ftheta_rec), B, C, N,
              int(image_width), int(image_height), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
-             alpha, beta, kappa, margin, int(all_valid), ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps))
+             alpha, beta, kappa, margin, int(all_valid), radii, means2d, depths, conics, comps)
         return radii, means2d, depths, conics, comps
-    call("gsx_project_ut_fwd", ptr(means.contiguous()), ptr(quats.contiguous()), ptr(scales.contiguous()),
-         ptr(_c(opacities)), ptr(viewmats0.contiguous()), ptr(Ks.contiguous()), ptr(_c(radial_coeffs)),
-         ptr(_c(tangential_coeffs)), ptr(_c(thin_prism_coeffs)), ptr(max_angle), B, C, N, int(image_width),
-         int(image_height),
-         float(eps2d), float(near_plane), float(far_plane), float(radius_clip), int(camera_model), alpha, beta, kappa,
-         margin, int(all_valid), ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps))
+    call("gsx_project_ut_fwd", means.contiguous(), quats.contiguous(), scales.contiguous(), _c(opacities),
+         viewmats0.contiguous(), Ks.contiguous(), _c(radial_coeffs), _c(tangential_coeffs), _c(thin_prism_coeffs), max_angle, B,
+         C, N, int(image_width), int(image_height), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
+         int(camera_model), alpha, beta, kappa, margin, int(all_valid), radii, means2d, depths, conics, comps)
     return radii, means2d, depths, conics, comps
 
 
@@ -2086,7 +2072,7 @@ def distort_camera_rays(rays, horizontal_poly, vertical_poly, horizontal_poly_in
     h, v = (base + 4 * 42, base + 4 * 63) if inverse else (base, base + 4 * 21)
     rays = rays.contiguous()
     out = torch.empty_like(rays)
-    call("gsx_distort_camera_rays", ptr(rays), rays.numel() // 3, h, v, ptr(out))
+    call("gsx_distort_camera_rays", rays, rays.numel() // 3, h, v, out)
     return out
 
 
@@ -2103,7 +2089,7 @@ def eval_bivariate_poly(x, y, poly_coeffs, order):
     rec = _windshield_record(one)
     x, y = x.contiguous(), y.contiguous()
     out = torch.empty_like(x)
-    call("gsx_eval_bivariate_poly", ptr(x), ptr(y), x.numel(), ctypes.addressof(rec), ptr(out))
+    call("gsx_eval_bivariate_poly", x, y, x.numel(), ctypes.addressof(rec), out)
     return out
 
 
@@ -2144,10 +2130,10 @@ def camera_pixel_rays(viewmats: Tensor, viewmats_rs: Optional[Tensor], Ks: Tenso
     _check_f32(viewmats=viewmats, viewmats_rs=viewmats_rs, Ks=Ks, radial_coeffs=radial_coeffs,
                tangential_coeffs=tangential_coeffs, thin_prism_coeffs=thin_prism_coeffs)
     rays = torch.empty(lead + (int(height), int(width), 6), device=dev, dtype=dt)
-    head = (ptr(viewmats.contiguous()), ptr(_c(viewmats_rs)) if rolling else None, ptr(Ks.contiguous()),
-            ptr(_c(radial_coeffs)), ptr(_c(tangential_coeffs)), ptr(_c(thin_prism_coeffs)), ptr(max_angle),
+    head = (viewmats.contiguous(), _c(viewmats_rs) if rolling else None, Ks.contiguous(),
+            _c(radial_coeffs), _c(tangential_coeffs), _c(thin_prism_coeffs), max_angle,
             ctypes.addressof(ftheta_rec) if ftheta_rec is not None else None)
-    tail = (I, int(width), int(height), int(camera_model), int(rs_type), ptr(rays))
+    tail = (I, int(width), int(height), int(camera_model), int(rs_type), rays)
     if external_distortion_params is not None:  # behind a windshield: the camera model's ray goes through the inverse polynomials
         ext = _windshield_record(external_distortion_params)
         call("gsx_camera_rays_ext", *head, ctypes.addressof(ext), *tail)
@@ -2184,9 +2170,8 @@ class _FromWorldCompositing(torch.autograd.Function):
         off, fl = tile_offsets.contiguous(), flatten_ids.contiguous()
         counts = torch.empty(batch + (C, height, width), device=dev, dtype=torch.int32) if want_counts else None
         normals = torch.empty(batch + (C, height, width, 3), device=dev, dtype=dt) if want_normals else None
-        call("gsx_raster_world_fwd_ex", *[ptr(t) for t in args], ptr(bg), ptr(mk), ptr(off), ptr(fl), I, C, N, fl.numel(), D,
-             int(width), int(height), int(tile_size), tw, th, int(bool(hit_distance)), ptr(renders), ptr(alphas), ptr(last_ids),
-             ptr(counts), ptr(normals))
+        call("gsx_raster_world_fwd_ex", *args, bg, mk, off, fl, I, C, N, fl.numel(), D, int(width), int(height), int(tile_size),
+             tw, th, int(bool(hit_distance)), renders, alphas, last_ids, counts, normals)
         ctx.save_for_backward(*args, off, fl, alphas, last_ids, *([bg] if bg is not None else []),
                               *([mk] if mk is not None else []))
         ctx.flags = (bg is not None, mk is not None, I, C, N, D, int(width), int(height), int(tile_size), tw, th, batch)
@@ -2220,13 +2205,12 @@ class _FromWorldCompositing(torch.autograd.Function):
         if extra:
             v_n = None if (v_normals is None or not want_normals) else v_normals.contiguous()
             v_rays = torch.zeros(ctx.rays_shape, device=means.device, dtype=means.dtype) if want_rays else None
-            call("gsx_raster_world_bwd_ex", ptr(means), ptr(quats), ptr(scales), ptr(colors), ptr(opacities), ptr(rays), ptr(bg),
-                 ptr(mk), ptr(off), ptr(fl), ptr(alphas), ptr(last_ids), ptr(v_r), ptr(v_a), ptr(v_n), I, C, N, fl.numel(), D,
-                 width, height, tile_size, tw, th, int(hit_distance), ptr(rows), width_rows, ptr(v_rays))
+            call("gsx_raster_world_bwd_ex", means, quats, scales, colors, opacities, rays, bg,
+                 mk, off, fl, alphas, last_ids, v_r, v_a, v_n, I, C, N, fl.numel(), D,
+                 width, height, tile_size, tw, th, int(hit_distance), rows, width_rows, v_rays)
         else:
-            call("gsx_raster_world_bwd", ptr(means), ptr(quats), ptr(scales), ptr(colors), ptr(opacities), ptr(rays), ptr(bg),
-                 ptr(mk), ptr(off), ptr(fl), ptr(alphas), ptr(last_ids), ptr(v_r), ptr(v_a), I, C, N, fl.numel(), D, width,
-                 height, tile_size, tw, th, ptr(rows), width_rows)
+            call("gsx_raster_world_bwd", means, quats, scales, colors, opacities, rays, bg, mk, off, fl, alphas, last_ids, v_r,
+                 v_a, I, C, N, fl.numel(), D, width, height, tile_size, tw, th, rows, width_rows)
         B = I // C
         per = rows.view(B, C, N, width_rows)
         v_means = per[..., 0:3].sum(1).reshape(means.shape)

@@ -118,8 +118,8 @@ class _FusedAppearance(torch.autograd.Function):
             bias1 = b1[None].expand(C, -1).contiguous()
         colors = torch.empty((C, N, 3), device=features.device, dtype=torch.float32)
         sd = (ctypes.c_int64 * 3)(*dirs.stride())
-        _cabi.call("gsx_appearance_fwd", _cabi.ptr(feats), _cabi.ptr_strided(dirs), sd, _cabi.ptr(bias1), _cabi.ptr(W1c),
-                   embed_dim, _cabi.ptr(W2c), _cabi.ptr(b2c), _cabi.ptr(W3c), _cabi.ptr(b3c), N, C, sh_degree, _cabi.ptr(colors))
+        _cabi.call("gsx_appearance_fwd", feats, _cabi.strided(dirs), sd, bias1, W1c,
+                   embed_dim, W2c, b2c, W3c, b3c, N, C, sh_degree, colors)
         _FusedAppearance.calls += 1
         ctx.save_for_backward(feats, dirs, emb, bias1, W1c, W2c, b2c, W3c, b3c)
         ctx.sh_degree, ctx.embed_dim = sh_degree, embed_dim
@@ -137,17 +137,15 @@ class _FusedAppearance(torch.autograd.Function):
         E = ctx.embed_dim
         dev = feats.device
         v_colors = v_colors.to(torch.float32).contiguous()
-        work = torch.empty(_cabi.appearance_bwd_workspace_floats(N, C), device=dev, dtype=torch.float32)
+        work = torch.empty(_cabi.query("gsx_appearance_bwd_workspace_floats", N, C), device=dev, dtype=torch.float32)
         v_features = torch.empty_like(feats)
         v_dirs = torch.empty((C, N, 3), device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
         v_W1x = torch.empty((64, 64), device=dev, dtype=torch.float32)
         v_W2 = torch.empty((64, 64), device=dev, dtype=torch.float32)
         v_small = torch.empty(260 + 64 * C, device=dev, dtype=torch.float32)
         sd = (ctypes.c_int64 * 3)(*dirs.stride())
-        _cabi.call("gsx_appearance_bwd", _cabi.ptr(feats), _cabi.ptr_strided(dirs), sd, _cabi.ptr(emb), _cabi.ptr(bias1),
-                   _cabi.ptr(W1), E, _cabi.ptr(W2), _cabi.ptr(b2), _cabi.ptr(W3), _cabi.ptr(b3), N, C, ctx.sh_degree,
-                   _cabi.ptr(v_colors), _cabi.ptr(work), _cabi.ptr(v_features), _cabi.ptr(v_dirs), _cabi.ptr(v_W1x),
-                   _cabi.ptr(v_W2), _cabi.ptr(v_small))
+        _cabi.call("gsx_appearance_bwd", feats, _cabi.strided(dirs), sd, emb, bias1, W1, E, W2, b2, W3, b3, N, C, ctx.sh_degree,
+                   v_colors, work, v_features, v_dirs, v_W1x, v_W2, v_small)
         v_b2, v_W3, v_b3 = v_small[:64], v_small[64:256].view(3, 64), v_small[256:259]
         s = v_small[260:].view(C, 64)  # per camera: the sum over the Gaussians of the gradient at layer 1's pre-activation
         v_b1 = s.sum(0)

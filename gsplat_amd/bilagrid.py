@@ -142,9 +142,8 @@ class _FusedSlice(torch.autograd.Function):
         mats = torch.empty((I, H, W, 12), device=rgb.device, dtype=torch.float32) if want_mats else None
         sr = (ctypes.c_int64 * 4)(*rgb.stride())
         sx = (ctypes.c_int64 * 4)(*xy.stride()) if xy is not None else None
-        _cabi.call("gsx_bilagrid_slice_fwd", _cabi.ptr(grids_c), N, L, Hg, Wg, _cabi.ptr_strided(rgb), sr,
-                   _cabi.ptr_strided(xy) if xy is not None else None, sx, _cabi.ptr(idx), I, H, W, _cabi.ptr(rgb_out),
-                   _cabi.ptr(mats))
+        _cabi.call("gsx_bilagrid_slice_fwd", grids_c, N, L, Hg, Wg, _cabi.strided(rgb), sr,
+                   _cabi.strided(xy) if xy is not None else None, sx, idx, I, H, W, rgb_out, mats)
         _FusedSlice.calls += 1
         ctx.save_for_backward(grids_c, rgb, xy, idx)
         if mats is None:
@@ -173,9 +172,8 @@ class _FusedSlice(torch.autograd.Function):
             return None, None, None, None, None
         sr, sv = (ctypes.c_int64 * 4)(*rgb.stride()), (ctypes.c_int64 * 4)(*v_out.stride())
         sx = (ctypes.c_int64 * 4)(*xy.stride()) if xy is not None else None
-        _cabi.call("gsx_bilagrid_slice_bwd", _cabi.ptr(grids), N, L, Hg, Wg, _cabi.ptr_strided(rgb), sr,
-                   _cabi.ptr_strided(xy) if xy is not None else None, sx, _cabi.ptr(idx), I, H, W, _cabi.ptr_strided(v_out), sv,
-                   _cabi.ptr(v_rgb), _cabi.ptr(v_grids))
+        _cabi.call("gsx_bilagrid_slice_bwd", grids, N, L, Hg, Wg, _cabi.strided(rgb), sr,
+                   _cabi.strided(xy) if xy is not None else None, sx, idx, I, H, W, _cabi.strided(v_out), sv, v_rgb, v_grids)
         return v_grids, v_rgb, None, None, None
 
 

@@ -88,7 +88,7 @@ def _fused_ok(img: Tensor, ref: Tensor) -> bool:
 def _scratch(n: int, device) -> Tensor:
     from . import _cabi
 
-    return torch.empty(195 * _cabi._lib.gsx_cc_blocks(n), device=device, dtype=torch.float64)  # GSX_CC_PARTIALS
+    return torch.empty(195 * _cabi.query("gsx_cc_blocks", n), device=device, dtype=torch.float64)  # GSX_CC_PARTIALS
 
 
 class _FusedColorCorrectQuadratic:
@@ -105,8 +105,7 @@ class _FusedColorCorrectQuadratic:
         out = torch.empty_like(x)
         warps = torch.empty((num_iters, 10, 3), device=dev, dtype=torch.float64)
         status = torch.empty(1, device=dev, dtype=torch.int32)  # cleared by the entry point
-        _cabi.call("gsx_cc_quadratic", _cabi.ptr(x), _cabi.ptr(r), n, num_iters, float(eps), _cabi.ptr(_scratch(n, dev)),
-                   _cabi.ptr(warps), _cabi.ptr(status), _cabi.ptr(out))
+        _cabi.call("gsx_cc_quadratic", x, r, n, num_iters, float(eps), _scratch(n, dev), warps, status, out)
         _FusedColorCorrectQuadratic.calls += 1
         bits = int(status.item())  # the one host read of the call
         if bits:
@@ -129,7 +128,7 @@ class _FusedColorCorrectAffine:
         n, dev = x.shape[0], x.device
         out = torch.empty_like(x)
         coef = torch.empty((3, 2), device=dev, dtype=torch.float64)
-        _cabi.call("gsx_cc_affine", _cabi.ptr(x), _cabi.ptr(r), n, _cabi.ptr(_scratch(n, dev)), _cabi.ptr(coef), _cabi.ptr(out))
+        _cabi.call("gsx_cc_affine", x, r, n, _scratch(n, dev), coef, out)
         _FusedColorCorrectAffine.calls += 1
         return out.reshape(img.shape)
 

@@ -146,8 +146,7 @@ def _assign_fused(x: Tensor, centroids: Tensor, want_best: bool) -> Tuple[Tensor
         labels = torch.empty(n, dtype=torch.int32, device=x.device)
         best = torch.empty(n, dtype=torch.float32, device=x.device) if want_best else None
         if n:
-            _cabi.call("gsx_kmeans_assign_l1", _cabi.ptr(x), n, d, _cabi.ptr(centroids), centroids.shape[0], _cabi.ptr(labels),
-                       _cabi.ptr(best))
+            _cabi.call("gsx_kmeans_assign_l1", x, n, d, centroids, centroids.shape[0], labels, best)
     return labels, best
 
 
@@ -165,9 +164,8 @@ def _update_fused(x: Tensor, labels: Tensor, centroids: Tensor) -> Tuple[Tensor,
         new = torch.empty_like(centroids)
         counts = torch.empty(k, dtype=torch.int32, device=x.device)
         shift = torch.empty(1, dtype=torch.float32, device=x.device)
-        work = torch.empty(_cabi.kmeans_workspace_bytes(n, d, k), dtype=torch.uint8, device=x.device)
-        _cabi.call("gsx_kmeans_update", _cabi.ptr(x), n, d, _cabi.ptr(labels), _cabi.ptr(keys), k, _cabi.ptr(centroids),
-                   _cabi.ptr(new), _cabi.ptr(counts), _cabi.ptr(shift), _cabi.ptr(work))
+        work = torch.empty(_cabi.query("gsx_kmeans_workspace_bytes", n, d, k), dtype=torch.uint8, device=x.device)
+        _cabi.call("gsx_kmeans_update", x, n, d, labels, keys, k, centroids, new, counts, shift, work)
     return new, counts, shift
 
 

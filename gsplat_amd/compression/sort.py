@@ -250,8 +250,8 @@ def _blur_fused(grid: Tensor, r: int, target: Tensor = None, work: Tensor = None
     with torch.cuda.device(grid.device):
         target = torch.empty_like(grid) if target is None else target
         if work is None:
-            work = torch.empty(_cabi.plas_workspace_bytes(H, W, c), dtype=torch.uint8, device=grid.device)
-        _cabi.call("gsx_plas_blur", _cabi.ptr(grid), H, W, c, r, _cabi.ptr(target), _cabi.ptr(work))
+            work = torch.empty(_cabi.query("gsx_plas_workspace_bytes", H, W, c), dtype=torch.uint8, device=grid.device)
+        _cabi.call("gsx_plas_blur", grid, H, W, c, r, target, work)
     return target
 
 
@@ -264,10 +264,9 @@ def _step_fused(grid: Tensor, target: Tensor, index: Tensor, b: int, seed: int, 
     H, W, c = grid.shape
     with torch.cuda.device(grid.device):
         if partials is None:
-            partials = torch.empty(_cabi.plas_partials_floats(H, W), dtype=torch.float32, device=grid.device)
+            partials = torch.empty(_cabi.query("gsx_plas_partials_floats", H, W), dtype=torch.float32, device=grid.device)
         result = torch.empty(2, dtype=torch.float32, device=grid.device) if result is None else result
-        _cabi.call("gsx_plas_step", _cabi.ptr(grid), _cabi.ptr(target), _cabi.ptr(index), H, W, c, b, seed & _M32, t & _M32,
-                   _cabi.ptr(partials), _cabi.ptr(result))
+        _cabi.call("gsx_plas_step", grid, target, index, H, W, c, b, seed & _M32, t & _M32, partials, result)
     return result
 
 
@@ -283,8 +282,8 @@ def _plas_sort_fused(feats, H, W, seed, improvement_break, radius_decay, max_ste
     if n:
         with torch.cuda.device(dev):
             target = torch.empty_like(grid)
-            work = torch.empty(_cabi.plas_workspace_bytes(H, W, c), dtype=torch.uint8, device=dev)
-            partials = torch.empty(_cabi.plas_partials_floats(H, W), dtype=torch.float32, device=dev)
+            work = torch.empty(_cabi.query("gsx_plas_workspace_bytes", H, W, c), dtype=torch.uint8, device=dev)
+            partials = torch.empty(_cabi.query("gsx_plas_partials_floats", H, W), dtype=torch.float32, device=dev)
             result = torch.empty(2, dtype=torch.float32, device=dev)
 
         def step(r, b, t):

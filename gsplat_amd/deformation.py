@@ -73,9 +73,8 @@ class _FusedDeform(torch.autograd.Function):
         W1c, b1c, W2c, b2c, W3c, b3c = (t.contiguous() for t in (W1, b1, W2, b2, W3, b3))
         Wh, bh = torch.cat([Wp, Wq, Wo], dim=0), torch.cat([bp, bq, bo], dim=0)
         outs = tuple(torch.empty((N, k), device=means.device, dtype=torch.float32) for k in (3, 4, 1))
-        mc, qc, oc = means.contiguous(), quats.contiguous(), opacities.contiguous()  # named: alive until the launch is queued
-        _cabi.call("gsx_deform_fwd", _cabi.ptr(mc), _cabi.ptr(qc), _cabi.ptr(oc), _cabi.ptr(x), _cabi.ptr(W1c), _cabi.ptr(b1c), _cabi.ptr(W2c), _cabi.ptr(b2c),
-                   _cabi.ptr(W3c), _cabi.ptr(b3c), _cabi.ptr(Wh), _cabi.ptr(bh), N, *(_cabi.ptr(o) for o in outs))
+        _cabi.call("gsx_deform_fwd", means.contiguous(), quats.contiguous(), opacities.contiguous(), x, W1c, b1c, W2c, b2c, W3c,
+                   b3c, Wh, bh, N, *outs)
         _FusedDeform.calls += 1
         ctx.set_materialize_grads(False)  # the cotangent of an output the loss does not use stays None
         ctx.save_for_backward(x, W1c, b1c, W2c, b2c, W3c, b3c, Wh, bh)
@@ -90,13 +89,11 @@ class _FusedDeform(torch.autograd.Function):
         N, dev = x.shape[0], x.device
         # a missing cotangent (an output the loss does not use) is a null pointer: zeros to the kernel, None to the caller
         cot = [None if v is None else v.to(torch.float32).contiguous() for v in (v_means, v_quats, v_opacities)]
-        work = torch.empty(_cabi.deform_bwd_workspace_floats(N), device=dev, dtype=torch.float32)
+        work = torch.empty(_cabi.query("gsx_deform_bwd_workspace_floats", N), device=dev, dtype=torch.float32)
         v_x = torch.empty_like(x) if ctx.needs_input_grad[3] else None
         v_W = torch.empty((3, 64, 64), device=dev, dtype=torch.float32)
         v_small = torch.empty(712, device=dev, dtype=torch.float32)
-        _cabi.call("gsx_deform_bwd", _cabi.ptr(x), _cabi.ptr(W1), _cabi.ptr(b1), _cabi.ptr(W2), _cabi.ptr(b2), _cabi.ptr(W3),
-                   _cabi.ptr(b3), _cabi.ptr(Wh), _cabi.ptr(bh), N, _cabi.ptr(cot[0]), _cabi.ptr(cot[1]), _cabi.ptr(cot[2]),
-                   _cabi.ptr(work), _cabi.ptr(v_x), _cabi.ptr(v_W), _cabi.ptr(v_small))
+        _cabi.call("gsx_deform_bwd", x, W1, b1, W2, b2, W3, b3, Wh, bh, N, *cot, work, v_x, v_W, v_small)
         v_b1, v_b2, v_b3 = v_small[:64], v_small[64:128], v_small[128:192]
         v_Wh, v_bh = v_small[192:704].view(8, 64), v_small[704:712]
         return (v_means, v_quats, v_opacities, v_x, v_W[0], v_b1.clone(), v_W[1], v_b2.clone(), v_W[2], v_b3.clone(),

@@ -93,14 +93,13 @@ def _knn_fused(x: Tensor, K: int, return_indices: bool, ring_cap: int = RING_CAP
     x = x.detach().contiguous()
     N = x.shape[0]
     with torch.cuda.device(x.device):
-        work = torch.empty(_cabi.knn_workspace_bytes(N, K), dtype=torch.uint8, device=x.device)
+        work = torch.empty(_cabi.query("gsx_knn_workspace_bytes", N, K), dtype=torch.uint8, device=x.device)
         keys = torch.empty(N, dtype=torch.int64, device=x.device)
-        _cabi.call("gsx_knn_bin", _cabi.ptr(x), N, _cabi.ptr(work), _cabi.ptr(keys))
+        _cabi.call("gsx_knn_bin", x, N, work, keys)
         keys = torch.sort(keys).values
         dist = torch.empty((N, K), dtype=torch.float32, device=x.device)
         idx = torch.empty((N, K), dtype=torch.int64, device=x.device) if return_indices else None
-        _cabi.call("gsx_knn_search", _cabi.ptr(x), _cabi.ptr(keys), N, K, int(ring_cap), _cabi.ptr(work), _cabi.ptr(dist),
-                   _cabi.ptr(idx))
+        _cabi.call("gsx_knn_search", x, keys, N, K, int(ring_cap), work, dist, idx)
     _last_work = work
     return (dist, idx) if return_indices else dist
 

@@ -66,12 +66,11 @@ class _FusedSsimMean(torch.autograd.Function):
         B, C, H, W = img1.shape
         img2 = img2.detach()
         dev = img1.device
-        partial = torch.empty(_cabi._lib.gsx_ssim_blocks(B, C, H, W), device=dev, dtype=torch.float32)
+        partial = torch.empty(_cabi.query("gsx_ssim_blocks", B, C, H, W), device=dev, dtype=torch.float32)
         need_grad = ctx.needs_input_grad[0]
         dmaps = torch.empty((B, C, H, W, 3), device=dev, dtype=torch.float32) if need_grad else None
         s1, s2 = (ctypes.c_int64 * 4)(*img1.stride()), (ctypes.c_int64 * 4)(*img2.stride())
-        _cabi.call("gsx_ssim_fwd", _cabi.ptr_strided(img1), s1, _cabi.ptr_strided(img2), s2, B, C, H, W, _cabi.ptr(partial),
-                   _cabi.ptr(dmaps))
+        _cabi.call("gsx_ssim_fwd", _cabi.strided(img1), s1, _cabi.strided(img2), s2, B, C, H, W, partial, dmaps)
         ctx.save_for_backward(img1, img2, dmaps)
         return partial.sum() / float(B * C * H * W)
 
@@ -89,8 +88,8 @@ class _FusedSsimMean(torch.autograd.Function):
         v_img1 = torch.empty_like(img1)  # preserve_format: a dense permuted view (channels-last render) keeps its strides
         s1, s2, sv = ((ctypes.c_int64 * 4)(*t.stride()) for t in (img1, img2, v_img1))
         v_mean = v_mean.reshape(1).to(torch.float32).contiguous()  # stays on the device: the kernel multiplies by it
-        _cabi.call("gsx_ssim_bwd", _cabi.ptr_strided(img1), s1, _cabi.ptr_strided(img2), s2, B, C, H, W, _cabi.ptr(dmaps),
-                   1.0 / float(B * C * H * W), _cabi.ptr(v_mean), _cabi.ptr_strided(v_img1), sv)
+        _cabi.call("gsx_ssim_bwd", _cabi.strided(img1), s1, _cabi.strided(img2), s2, B, C, H, W, dmaps,
+                   1.0 / float(B * C * H * W), v_mean, _cabi.strided(v_img1), sv)
         return v_img1, None
 
 
@@ -161,15 +160,15 @@ class _FusedPhotometric(torch.autograd.Function):
                 mask = mask.to(torch.float32)
             mask = mask.expand(B, C, H, W)  # stride 0 along the broadcast dimensions: read in place
         tag = 1 if mask is not None and mask.dtype == torch.uint8 else 0  # GSX_MASK_U8 / GSX_MASK_F32
-        partial = torch.empty(3 * _cabi._lib.gsx_photometric_blocks(B, C, H, W), device=dev, dtype=torch.float32)
+        partial = torch.empty(3 * _cabi.query("gsx_photometric_blocks", B, C, H, W), device=dev, dtype=torch.float32)
         record = torch.empty(4, device=dev, dtype=torch.float32)
         need_grad = ctx.needs_input_grad[0]
         dmaps = torch.empty((B, C, H, W, 3), device=dev, dtype=torch.float32) if need_grad else None
         sp, st = (ctypes.c_int64 * 4)(*pred.stride()), (ctypes.c_int64 * 4)(*target.stride())
         sm = (ctypes.c_int64 * 4)(*mask.stride()) if mask is not None else None
-        _cabi.call("gsx_photometric_fwd", _cabi.ptr_strided(pred), sp, _cabi.ptr_strided(target), st,
-                   _cabi.ptr_strided(mask) if mask is not None else None, sm, tag, B, C, H, W, float(ssim_lambda),
-                   _cabi.ptr(partial), _cabi.ptr(dmaps), _cabi.ptr(record))
+        _cabi.call("gsx_photometric_fwd", _cabi.strided(pred), sp, _cabi.strided(target), st,
+                   _cabi.strided(mask) if mask is not None else None, sm, tag, B, C, H, W, float(ssim_lambda),
+                   partial, dmaps, record)
         _FusedPhotometric.calls += 1
         ctx.save_for_backward(pred, target, mask, dmaps, record)
         ctx.ssim_lambda, ctx.mask_tag = float(ssim_lambda), tag
@@ -193,9 +192,9 @@ class _FusedPhotometric(torch.autograd.Function):
         sp, st, sv = ((ctypes.c_int64 * 4)(*t.stride()) for t in (pred, target, v_pred))
         sm = (ctypes.c_int64 * 4)(*mask.stride()) if mask is not None else None
         v_loss = v_loss.reshape(1).to(torch.float32).contiguous()  # stays on the device: the kernel multiplies by it
-        _cabi.call("gsx_photometric_bwd", _cabi.ptr_strided(pred), sp, _cabi.ptr_strided(target), st,
-                   _cabi.ptr_strided(mask) if mask is not None else None, sm, ctx.mask_tag, B, C, H, W, ctx.ssim_lambda,
-                   _cabi.ptr(dmaps), _cabi.ptr(record), _cabi.ptr(v_loss), _cabi.ptr_strided(v_pred), sv)
+        _cabi.call("gsx_photometric_bwd", _cabi.strided(pred), sp, _cabi.strided(target), st,
+                   _cabi.strided(mask) if mask is not None else None, sm, ctx.mask_tag, B, C, H, W, ctx.ssim_lambda,
+                   dmaps, record, v_loss, _cabi.strided(v_pred), sv)
         return v_pred, None, None, None
 
 
@@ -260,9 +259,9 @@ class _FusedTotalVariation(torch.autograd.Function):
         from . import _cabi
 
         xc = x.contiguous()
-        partial = torch.empty(_cabi._lib.gsx_tv_blocks(*xc.shape), device=x.device, dtype=torch.float32)
+        partial = torch.empty(_cabi.query("gsx_tv_blocks", *xc.shape), device=x.device, dtype=torch.float32)
         out = torch.empty(1, device=x.device, dtype=torch.float32)
-        _cabi.call("gsx_tv_fwd", _cabi.ptr(xc), *xc.shape, _cabi.ptr(partial), _cabi.ptr(out))
+        _cabi.call("gsx_tv_fwd", xc, *xc.shape, partial, out)
         _FusedTotalVariation.calls += 1
         ctx.save_for_backward(xc)
         return out[0]
@@ -275,7 +274,7 @@ class _FusedTotalVariation(torch.autograd.Function):
         (xc,) = ctx.saved_tensors
         v_x = torch.empty_like(xc)
         v_loss = v_loss.reshape(1).to(torch.float32).contiguous()  # stays on the device: the kernel multiplies by it
-        _cabi.call("gsx_tv_bwd", _cabi.ptr(xc), *xc.shape, _cabi.ptr(v_loss), _cabi.ptr(v_x))
+        _cabi.call("gsx_tv_bwd", xc, *xc.shape, v_loss, v_x)
         return v_x
 
 
@@ -407,14 +406,14 @@ def _dense_depth_args(pred4: Tensor, gt4: Tensor, mask4, tag: int):
 
     sp, sg = (ctypes.c_int64 * 4)(*pred4.stride()), (ctypes.c_int64 * 4)(*gt4.stride())
     sm = (ctypes.c_int64 * 4)(*mask4.stride()) if mask4 is not None else None
-    return (_cabi.ptr_strided(pred4), sp, _cabi.ptr_strided(gt4), sg, _cabi.ptr_strided(mask4) if mask4 is not None else None, sm,
+    return (_cabi.strided(pred4), sp, _cabi.strided(gt4), sg, _cabi.strided(mask4) if mask4 is not None else None, sm,
             tag, *pred4.shape)
 
 
 def _depth_scratch(n: int, device):
     from . import _cabi
 
-    partial = torch.empty(6 * _cabi._lib.gsx_depth_blocks(n), device=device, dtype=torch.float64)  # GSX_DEPTH_PARTIALS
+    partial = torch.empty(6 * _cabi.query("gsx_depth_blocks", n), device=device, dtype=torch.float64)  # GSX_DEPTH_PARTIALS
     return partial, torch.empty(1, device=device, dtype=torch.float32), torch.empty(8, device=device, dtype=torch.float64)
 
 
@@ -432,8 +431,7 @@ class _FusedPearsonDepth(torch.autograd.Function):
         pred4, gt4 = _as_4d(pred), _as_4d(gt.detach())
         mask4, tag = _mask_4d(mask, pred.shape)
         partial, loss, record = _depth_scratch(pred4.numel(), pred.device)
-        _cabi.call("gsx_depth_pearson_fwd", *_dense_depth_args(pred4, gt4, mask4, tag), _cabi.ptr(partial), _cabi.ptr(loss),
-                   _cabi.ptr(record))
+        _cabi.call("gsx_depth_pearson_fwd", *_dense_depth_args(pred4, gt4, mask4, tag), partial, loss, record)
         _FusedPearsonDepth.calls += 1
         ctx.save_for_backward(pred4, gt4, mask4, record)
         ctx.mask_tag, ctx.shape = tag, pred.shape
@@ -450,8 +448,7 @@ class _FusedPearsonDepth(torch.autograd.Function):
             return None, None, None
         v_pred = torch.empty(pred4.shape, device=pred4.device, dtype=torch.float32)
         v_loss = v_loss.reshape(1).to(torch.float32).contiguous()  # stays on the device: the kernel multiplies by it
-        _cabi.call("gsx_depth_pearson_bwd", *_dense_depth_args(pred4, gt4, mask4, ctx.mask_tag), _cabi.ptr(record),
-                   _cabi.ptr(v_loss), _cabi.ptr(v_pred))
+        _cabi.call("gsx_depth_pearson_bwd", *_dense_depth_args(pred4, gt4, mask4, ctx.mask_tag), record, v_loss, v_pred)
         return v_pred.view(ctx.shape), None, None
 
 
@@ -469,8 +466,8 @@ class _FusedDisparityL1(torch.autograd.Function):
         pred4, gt4 = _as_4d(pred), _as_4d(gt.detach())
         mask4, tag = _mask_4d(mask, pred.shape)
         partial, loss, record = _depth_scratch(pred4.numel(), pred.device)
-        _cabi.call("gsx_depth_disparity_fwd", *_dense_depth_args(pred4, gt4, mask4, tag), mode, scale, eps, _cabi.ptr(partial),
-                   _cabi.ptr(loss), _cabi.ptr(record))
+        _cabi.call("gsx_depth_disparity_fwd", *_dense_depth_args(pred4, gt4, mask4, tag), mode, scale, eps, partial,
+                   loss, record)
         _FusedDisparityL1.calls += 1
         ctx.save_for_backward(pred4, gt4, mask4, record)
         ctx.mask_tag, ctx.shape, ctx.mode, ctx.eps = tag, pred.shape, mode, eps
@@ -488,7 +485,7 @@ class _FusedDisparityL1(torch.autograd.Function):
         v_pred = torch.empty(pred4.shape, device=pred4.device, dtype=torch.float32)
         v_loss = v_loss.reshape(1).to(torch.float32).contiguous()  # stays on the device: the kernel multiplies by it
         _cabi.call("gsx_depth_disparity_bwd", *_dense_depth_args(pred4, gt4, mask4, ctx.mask_tag), ctx.mode, ctx.eps,
-                   _cabi.ptr(record), _cabi.ptr(v_loss), _cabi.ptr(v_pred))
+                   record, v_loss, v_pred)
         return v_pred.view(ctx.shape), None, None, None, None, None
 
 
@@ -506,8 +503,8 @@ class _FusedSampledDepthL1(torch.autograd.Function):
         from . import _cabi
 
         C, H, W = depth_map.shape
-        return (_cabi.ptr_strided(depth_map), (ctypes.c_int64 * 3)(*depth_map.stride()), C, H, W, _cabi.ptr(points),
-                _cabi.ptr(depths_gt), points.shape[1])
+        return (_cabi.strided(depth_map), (ctypes.c_int64 * 3)(*depth_map.stride()), C, H, W, points,
+                depths_gt, points.shape[1])
 
     @staticmethod
     def forward(ctx, depth_map: Tensor, points: Tensor, depths_gt: Tensor, scale: float):
@@ -516,8 +513,7 @@ class _FusedSampledDepthL1(torch.autograd.Function):
         map3 = depth_map[..., 0] if depth_map.dim() == 4 else depth_map
         points, depths_gt = points.detach().contiguous(), depths_gt.detach().contiguous()
         partial, loss, record = _depth_scratch(depths_gt.numel(), map3.device)
-        _cabi.call("gsx_depth_sampled_fwd", *_FusedSampledDepthL1._args(map3, points, depths_gt), scale, _cabi.ptr(partial),
-                   _cabi.ptr(loss), _cabi.ptr(record))
+        _cabi.call("gsx_depth_sampled_fwd", *_FusedSampledDepthL1._args(map3, points, depths_gt), scale, partial, loss, record)
         _FusedSampledDepthL1.calls += 1
         ctx.save_for_backward(map3, points, depths_gt, record)
         ctx.shape = depth_map.shape
@@ -534,8 +530,7 @@ class _FusedSampledDepthL1(torch.autograd.Function):
             return None, None, None, None
         v_map = torch.empty(map3.shape, device=map3.device, dtype=torch.float32)  # zero-filled by the entry point
         v_loss = v_loss.reshape(1).to(torch.float32).contiguous()  # stays on the device: the kernel multiplies by it
-        _cabi.call("gsx_depth_sampled_bwd", *_FusedSampledDepthL1._args(map3, points, depths_gt), _cabi.ptr(record),
-                   _cabi.ptr(v_loss), _cabi.ptr(v_map))
+        _cabi.call("gsx_depth_sampled_bwd", *_FusedSampledDepthL1._args(map3, points, depths_gt), record, v_loss, v_map)
         return v_map.view(ctx.shape), None, None, None
 
 

@@ -691,7 +691,7 @@ class _SurfelPost(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, colors, alphas, normals, median, viewmats, Ks, expected_depth: bool, depth_source: int):
-        from ._cabi import call, ptr
+        from ._cabi import call
 
         I = viewmats.numel() // 16
         H, W, D = colors.shape[-3], colors.shape[-2], colors.shape[-1]
@@ -701,8 +701,8 @@ class _SurfelPost(torch.autograd.Function):
         colors_out = torch.empty_like(colors) if expected_depth else None
         normals_world = torch.empty_like(normals)
         surf = torch.empty_like(normals) if depth_source else None
-        call("gsx_surfel_post_fwd", ptr(colors), ptr(alphas), ptr(normals), ptr(median), ptr(viewmats), ptr(Ks), I, W, H, D,
-             int(expected_depth), depth_source, ptr(colors_out), ptr(normals_world), ptr(surf))
+        call("gsx_surfel_post_fwd", colors, alphas, normals, median, viewmats, Ks, I, W, H, D,
+             int(expected_depth), depth_source, colors_out, normals_world, surf)
         ctx.save_for_backward(colors, alphas, normals, median, viewmats, Ks)
         ctx.cfg = (I, W, H, D, bool(expected_depth), depth_source)
         # an output the loss does not use gets None in backward, not a zero image: with no cotangent for the depth-map normals
@@ -719,7 +719,7 @@ class _SurfelPost(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_colors_out, v_normals_world, v_surf):
-        from ._cabi import call, ptr
+        from ._cabi import call
 
         colors, alphas, normals, median, viewmats, Ks = ctx.saved_tensors
         I, W, H, D, expected_depth, depth_source = ctx.cfg
@@ -731,9 +731,8 @@ class _SurfelPost(torch.autograd.Function):
         v_colors, v_normals = torch.empty_like(colors), torch.empty_like(normals)
         v_alphas = torch.empty_like(alphas) if expected_depth else None
         v_median = torch.empty_like(median) if depth_source == 2 else None
-        call("gsx_surfel_post_bwd", ptr(colors), ptr(alphas), ptr(normals), ptr(median), ptr(viewmats), ptr(Ks), I, W, H, D,
-             int(expected_depth), depth_source, ptr(v_colors_out), ptr(v_normals_world), ptr(v_surf), ptr(v_colors),
-             ptr(v_alphas), ptr(v_normals), ptr(v_median))
+        call("gsx_surfel_post_bwd", colors, alphas, normals, median, viewmats, Ks, I, W, H, D, int(expected_depth),
+             depth_source, v_colors_out, v_normals_world, v_surf, v_colors, v_alphas, v_normals, v_median)
         return v_colors, v_alphas, v_normals, v_median, None, None, None, None
 
 

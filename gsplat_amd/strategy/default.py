@@ -159,13 +159,13 @@ class DefaultStrategy(Strategy):
                 if shp[d] != 1 and st[d] != expect:
                     return False
                 expect *= shp[d]
-        from .._cabi import call, ptr, ptr_strided
+        from .._cabi import call, strided
 
         C = grad.numel() // (2 * n)
-        call("gsx_strategy_accumulate", ptr_strided(grad) if rows is None else ptr(rows), int(stride), ptr(radii), C, n,
+        call("gsx_strategy_accumulate", strided(grad) if rows is None else rows, int(stride), radii, C, n,
              0.5 * info["width"] * info["n_cameras"], 0.5 * info["height"] * info["n_cameras"],
-             1.0 / float(max(info["width"], info["height"])), ptr(state["grad2d"]), ptr(state["count"]),
-             ptr(state["radii"]) if track else None)
+             1.0 / float(max(info["width"], info["height"])), state["grad2d"], state["count"],
+             state["radii"] if track else None)
         return True
 
     # ---- one refinement = one plan -------------------------------------------------------------------------------------

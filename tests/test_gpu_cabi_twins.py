@@ -50,7 +50,7 @@ def _rand(g, *shape):
 def _call(name, *args):
     from gsplat_amd import _cabi
 
-    _cabi.call(name, *[_cabi.ptr(a) if (a is None or isinstance(a, torch.Tensor)) else a for a in args])
+    _cabi.call(name, *args)
 
 
 def _assert_sum(got, terms, dim, n, name):

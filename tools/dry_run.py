@@ -29,8 +29,7 @@ def install():
     from gsplat_amd import _cabi, _ops
 
     calls = []
-    _cabi.ptr = lambda t: None if t is None else t.data_ptr()
-    _cabi.ptr_strided = lambda t: t.data_ptr()
+    _cabi._refuse_host_tensor = lambda t: None  # CPU tensors stand in for device tensors
     _cabi.current_stream = lambda: 0
     real_call = _cabi.call
 
@@ -43,8 +42,7 @@ def install():
                 raise
 
     _cabi.call = call
-    for mod in (_ops,):
-        mod.ptr, mod.ptr_strided, mod.call = _cabi.ptr, _cabi.ptr_strided, call
+    _ops.call = call  # its imported copy
     cpu = torch.library.Library("gsplat", "IMPL", "CPU")
     for name in _ops.SCHEMAS:
         cpu.impl(name, _ops.impl(name) if name in _ops._impls else _compiled_on_cpu(name))
