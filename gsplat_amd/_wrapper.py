@@ -121,8 +121,9 @@ def rasterize_to_pixels_eval3d(
 ) -> Tuple[Tensor, Tensor]:
     """Like ``rasterize_to_pixels`` but every sample is the Gaussian's response along the pixel's ray in world space
     (reference ``gsplat/cuda/_wrapper.py:2263-2353``): perfect pinhole cameras or caller-provided ``rays``, global
-    shutter. Differentiable w.r.t. means / quats / scales / colors / opacities (rays, cameras and backgrounds are constants,
-    like the reference's from-world backward, RasterizeToPixelsFromWorld3DGSBwd.cu). Returns (render_colors, render_alphas)."""
+    shutter. Differentiable w.r.t. means / quats / scales / colors / opacities and - where they require grad - the caller's
+    ``rays`` (v_rays) and ``backgrounds`` (v_backgrounds); the cameras are constants (reference kernel
+    RasterizeToPixelsFromWorld3DGSBwd.cu). Returns (render_colors, render_alphas)."""
     models = {"pinhole": 0, "ortho": 1, "fisheye": 2, "ftheta": 3, "lidar": 4}
     c = lambda t: None if t is None else t.contiguous()  # noqa: E731
     cls = torch.classes.gsplat
