@@ -16,9 +16,11 @@ There is no CPU implementation: calling these ops with CPU tensors raises.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 import threading
+import types
 from typing import Optional, Tuple
 
 import torch
@@ -176,6 +178,10 @@ def _check_f32(**tensors):
 
 def _c(t: Optional[Tensor]) -> Optional[Tensor]:
     return None if t is None else t.contiguous()
+
+
+CAMERA_MODEL_IDS = {"pinhole": 0, "ortho": 1, "fisheye": 2, "ftheta": 3, "lidar": 4}  # CameraModelType (Common.h:75-82)
+ROLLING_SHUTTER_GLOBAL = 4  # RollingShutterType.GLOBAL (Cameras.h:38-45); 0 .. 3 are the rolling ones
 
 
 def _row_view(t: Tensor, width: int):
@@ -645,15 +651,20 @@ def intersect_tile(means2d, radii, depths, conics, opacities, image_ids, gaussia
                                     tile_size, tile_width, tile_height, sort, segmented))
 
 
+def _lidar_fov_args(lidar):
+    """(fields of view in radians: horizontal start, span, vertical start, span; spinning direction) as the lidar entries take them."""
+    return (float(lidar.fov_horiz_rad.start), float(lidar.fov_horiz_rad.span), float(lidar.fov_vert_rad.start),
+            float(lidar.fov_vert_rad.span), int(lidar.spinning_direction))
+
+
 def _lidar_tiling_args(lidar, dev):
     """(fields of view, direction, tiling sizes, the two tables on `dev`) of a RowOffsetStructuredSpinningLidarModelParametersExt."""
     cdf_el = lidar.cdf_elevation.to(device=dev, dtype=torch.int32).contiguous()
     raycdf = lidar.cdf_dense_ray_mask.to(device=dev, dtype=torch.int32).contiguous()
     if cdf_el.dim() != 1 or raycdf.dim() != 2 or raycdf.shape[0] != cdf_el.shape[0]:
         raise RuntimeError("lidar tiling: cdf_elevation [R + 1] and cdf_dense_ray_mask [R + 1, A + 1] expected")
-    return ((float(lidar.fov_horiz_rad.start), float(lidar.fov_horiz_rad.span), float(lidar.fov_vert_rad.start),
-             float(lidar.fov_vert_rad.span), int(lidar.spinning_direction), int(lidar.n_bins_azimuth), int(lidar.n_bins_elevation),
-             int(raycdf.shape[1] - 1), int(raycdf.shape[0] - 1), cdf_el, raycdf), (cdf_el, raycdf))
+    return ((*_lidar_fov_args(lidar), int(lidar.n_bins_azimuth), int(lidar.n_bins_elevation), int(raycdf.shape[1] - 1),
+             int(raycdf.shape[0] - 1), cdf_el, raycdf), (cdf_el, raycdf))
 
 
 @_op("intersect_tile_lidar")
@@ -1714,17 +1725,30 @@ def fisheye_max_angle(radial_coeffs: Tensor, Ks: Tensor, width: int, height: int
     return torch.minimum(angle, torch.maximum(corner / fx, corner / fy))
 
 
-def _lidar_fov_args(lidar):
-    return (float(lidar.fov_horiz_rad.start), float(lidar.fov_horiz_rad.span), float(lidar.fov_vert_rad.start),
-            float(lidar.fov_vert_rad.span))
-
-
 def _lidar_angle_map(lidar, dev):
     """angles_to_columns_map as int32 on `dev` (it maps a relative (elevation, azimuth) to the column that fires there)."""
     m = lidar.angles_to_columns_map
     if m is None or m.numel() == 0:
         return None
     return m.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _ut_scalars(ut_params):
+    """(alpha, beta, kappa, in_image_margin_factor, require_all_sigma_points_valid) of an UnscentedTransformParameters; None =
+    the record's defaults (Cameras.h:59-64)."""
+    if ut_params is None:
+        return 0.1, 2.0, 0.0, 0.1, 0
+    return (float(ut_params.alpha), float(ut_params.beta), float(ut_params.kappa), float(ut_params.in_image_margin_factor),
+            int(bool(ut_params.require_all_sigma_points_valid)))
+
+
+def _ut_outputs(means, rows, calc_compensations):
+    """The projection's outputs for rows = (..., C, N): radii [..., C, N, 2] int32, means2d [..., C, N, 2], depths [..., C, N],
+    conics [..., C, N, 3], compensations [..., C, N] or None."""
+    dev, dt = means.device, means.dtype
+    return (torch.empty(rows + (2,), device=dev, dtype=torch.int32), torch.empty(rows + (2,), device=dev, dtype=dt),
+            torch.empty(rows, device=dev, dtype=dt), torch.empty(rows + (3,), device=dev, dtype=dt),
+            torch.empty(rows, device=dev, dtype=dt) if calc_compensations else None)
 
 
 def _projection_ut_lidar(means, quats, scales, opacities, viewmats0, viewmats1, Ks, eps2d, near_plane, far_plane, radius_clip,
@@ -1735,38 +1759,27 @@ def _projection_ut_lidar(means, quats, scales, opacities, viewmats0, viewmats1, 
     if radial_coeffs is not None or tangential_coeffs is not None or thin_prism_coeffs is not None \
             or external_distortion_params is not None:
         raise RuntimeError("the lidar camera model takes no distortion coefficients")
-    rolling = rs_type != _ROLLING_SHUTTER_GLOBAL
-    if rolling and viewmats1 is None:
-        raise ValueError("a rolling shutter needs viewmats_rs (the pose at the end of the frame)")
+    rolling = rs_type != ROLLING_SHUTTER_GLOBAL
     _check_f32(means=means, quats=quats, scales=scales, opacities=opacities, viewmats=viewmats0, viewmats_rs=viewmats1, Ks=Ks)
     batch = tuple(means.shape[:-2])
-    N, C, B = means.shape[-2], viewmats0.shape[-3], math.prod(means.shape[:-2])
-    alpha, beta, kappa, margin, all_valid = 0.1, 2.0, 0.0, 0.1, False  # Cameras.h:59-64
-    if ut_params is not None:
-        alpha, beta, kappa = float(ut_params.alpha), float(ut_params.beta), float(ut_params.kappa)
-        margin, all_valid = float(ut_params.in_image_margin_factor), bool(ut_params.require_all_sigma_points_valid)
-    dev, dt = means.device, means.dtype
-    radii = torch.empty(batch + (C, N, 2), device=dev, dtype=torch.int32)
-    means2d = torch.empty(batch + (C, N, 2), device=dev, dtype=dt)
-    depths = torch.empty(batch + (C, N), device=dev, dtype=dt)
-    conics = torch.empty(batch + (C, N, 3), device=dev, dtype=dt)
-    comps = torch.empty(batch + (C, N), device=dev, dtype=dt) if calc_compensations else None
-    amap = _lidar_angle_map(lidar, dev) if rolling else None
+    N, C, B = means.shape[-2], viewmats0.shape[-3], math.prod(batch)
+    outs = _ut_outputs(means, batch + (C, N), calc_compensations)
+    amap = _lidar_angle_map(lidar, means.device) if rolling else None
     mh, mw = (int(amap.shape[0]), int(amap.shape[1])) if amap is not None else (0, 0)
     call("gsx_project_ut_lidar_fwd", means.contiguous(), quats.contiguous(), scales.contiguous(),
          _c(opacities), viewmats0.contiguous(), _c(viewmats1) if rolling else None, Ks.contiguous(),
-         *_lidar_fov_args(lidar), int(lidar.spinning_direction), amap, mh, mw, int(lidar.column_azimuths_rad.shape[0]), B, C,
-         N, float(eps2d), float(near_plane), float(far_plane), float(radius_clip), int(rs_type), int(bool(global_z_order)), alpha,
-         beta, kappa, margin, int(all_valid), radii, means2d, depths, conics, comps)
-    return radii, means2d, depths, conics, comps
+         *_lidar_fov_args(lidar), amap, mh, mw, int(lidar.column_azimuths_rad.shape[0]), B, C, N, float(eps2d),
+         float(near_plane), float(far_plane), float(radius_clip), int(rs_type), int(bool(global_z_order)),
+         *_ut_scalars(ut_params), *outs)
+    return outs
 
 
-def lidar_element_rays(viewmats: Tensor, viewmats_rs: Optional[Tensor], lidar, rs_type: int = 4) -> Tensor:
+def lidar_element_rays(viewmats: Tensor, viewmats_rs: Optional[Tensor], lidar, rs_type: int = ROLLING_SHUTTER_GLOBAL) -> Tensor:
     """[..., C, n_rows, n_columns, 6]: world ray of every element of a spinning lidar (gsx_lidar_rays) - the rays the reference's
     from-world kernels derive per thread for lidar elements; the zero ray outside the fields of view."""
     lead = tuple(viewmats.shape[:-2])
     dev, dt = viewmats.device, viewmats.dtype
-    rolling = rs_type != 4
+    rolling = rs_type != ROLLING_SHUTTER_GLOBAL
     if rolling and (viewmats_rs is None or viewmats_rs.shape != viewmats.shape):
         raise ValueError("a rolling shutter needs viewmats_rs of the shape of viewmats")
     rows = lidar.row_elevations_rad.to(device=dev, dtype=torch.float32).contiguous()
@@ -1775,9 +1788,10 @@ def lidar_element_rays(viewmats: Tensor, viewmats_rs: Optional[Tensor], lidar, r
     amap = _lidar_angle_map(lidar, dev) if rolling else None
     mh, mw = (int(amap.shape[0]), int(amap.shape[1])) if amap is not None else (0, 0)
     rays = torch.empty(lead + (rows.shape[0], cols.shape[0], 6), device=dev, dtype=dt)
+    *fov, ccw = _lidar_fov_args(lidar)
     call("gsx_lidar_rays", viewmats.contiguous(), _c(viewmats_rs) if rolling else None, rows, cols, offs,
-         math.prod(lead), int(rows.shape[0]), int(cols.shape[0]), *_lidar_fov_args(lidar), float(lidar.fov_eps_rad),
-         int(lidar.spinning_direction), amap, mh, mw, int(rs_type), rays)
+         math.prod(lead), int(rows.shape[0]), int(cols.shape[0]), *fov, float(lidar.fov_eps_rad), ccw, amap, mh, mw,
+         int(rs_type), rays)
     return rays
 
 
@@ -1809,219 +1823,9 @@ def _lidar_virtual_layout(lidar, dev):
     return S, tw * S, th * S, elem_flat[valid], virt_flat[valid]
 
 
-@_op("projection_ut_3dgs_fused")
-def projection_ut_3dgs_fused(means, quats, scales, opacities, viewmats0, viewmats1, Ks, image_width, image_height,
-                             eps2d, near_plane, far_plane, radius_clip, calc_compensations, camera_model, global_z_order,
-                             ut_params, rs_type, radial_coeffs, tangential_coeffs, thin_prism_coeffs, ftheta_coeffs,
-                             lidar_coeffs, external_distortion_params):
-    """gsplat::projection_ut_3dgs_fused (kernel ``ProjectionUT3DGSFused.cu``): perfect / OpenCV pinhole, orthographic, OpenCV
-    fisheye and f-theta cameras, global or rolling shutter, z or Euclidean sort depth. Lidar and external distortion are
-    refused, never approximated."""
-    rolling = rs_type != _ROLLING_SHUTTER_GLOBAL
-    if rolling and viewmats1 is None:
-        raise ValueError("a rolling shutter needs viewmats_rs (the pose at the end of the frame)")
-    if rs_type not in (0, 1, 2, 3, 4):
-        raise ValueError(f"unknown rolling shutter type {rs_type}")
-    if camera_model not in (0, 1, 2, 3, 4):
-        raise NotImplementedError(f"gsplat_amd: UT projection is built for pinhole, ortho, fisheye, f-theta and lidar cameras, not "
-                                  f"'{_CAMERA_MODEL_NAMES.get(camera_model, camera_model)}'")
-    if (camera_model == 4) != (lidar_coeffs is not None):
-        raise RuntimeError("Lidar coefficients must be given for lidar camera model" if camera_model == 4 else
-                           "lidar_coeffs given but camera_model is not lidar")
-    if camera_model == 4:
-        return _projection_ut_lidar(means, quats, scales, opacities, viewmats0, viewmats1, Ks, eps2d, near_plane, far_plane,
-                                    radius_clip, calc_compensations, global_z_order, ut_params, rs_type, lidar_coeffs,
-                                    radial_coeffs, tangential_coeffs, thin_prism_coeffs, external_distortion_params)
-    _check_f32(means=means, quats=quats, scales=scales, opacities=opacities, viewmats=viewmats0, viewmats_rs=viewmats1, Ks=Ks,
-               radial_coeffs=radial_coeffs, tangential_coeffs=tangential_coeffs, thin_prism_coeffs=thin_prism_coeffs)
-    batch = tuple(means.shape[:-2])
-    N, C, B = means.shape[-2], viewmats0.shape[-3], math.prod(means.shape[:-2])
-    if quats.shape != batch + (N, 4) or scales.shape != batch + (N, 3) or viewmats0.shape != batch + (C, 4, 4) \
-            or Ks.shape != batch + (C, 3, 3) or (opacities is not None and opacities.shape != batch + (N,)):
-        raise ValueError("projection_ut_3dgs_fused: inconsistent input shapes")
-    ftheta_rec = None
-    if camera_model == 3:  # f-theta: one parameter record per call, no OpenCV coefficients
-        if radial_coeffs is not None or tangential_coeffs is not None or thin_prism_coeffs is not None:
-            raise ValueError("the f-theta camera model takes ftheta_coeffs, not radial / tangential / thin-prism coefficients")
-        if ftheta_coeffs is None:
-            raise ValueError("camera_model='ftheta' needs ftheta_coeffs (FThetaCameraDistortionParameters)")
-        import ctypes
-
-        p2a, a2p = list(ftheta_coeffs.pixeldist_to_angle_poly), list(ftheta_coeffs.angle_to_pixeldist_poly)
-        cde = list(ftheta_coeffs.linear_cde)
-        if len(p2a) != 6 or len(a2p) != 6 or len(cde) != 3:
-            raise ValueError("ftheta_coeffs: the polynomials have 6 terms, linear_cde 3")
-        vals = [1.0 if int(ftheta_coeffs.reference_poly) != 0 else 0.0] + [float(v) for v in p2a] + [float(v) for v in a2p] \
-            + [float(ftheta_coeffs.max_angle)] + [float(v) for v in cde]
-        ftheta_rec = (ctypes.c_float * 17)(*vals)
-    max_angle = None
-    if camera_model == 2:  # fisheye: k1..k4 only, plus the per-camera angle limit
-        if tangential_coeffs is not None or thin_prism_coeffs is not None:
-            raise ValueError("the fisheye camera model takes radial_coeffs [..., C, 4] only")
-        if radial_coeffs is None:
-            radial_coeffs = torch.zeros(batch + (C, 4), device=means.device, dtype=means.dtype)
-        if radial_coeffs.shape != batch + (C, 4):
-            raise ValueError(f"fisheye radial_coeffs must have shape [..., C, 4], got {tuple(radial_coeffs.shape)}")
-        max_angle = fisheye_max_angle(radial_coeffs, Ks, int(image_width), int(image_height)).contiguous()
-    if radial_coeffs is not None:
-        if radial_coeffs.shape[:-1] != batch + (C,) or radial_coeffs.shape[-1] not in (4, 6):
-            raise ValueError(f"radial_coeffs must have shape [..., C, 6] or [..., C, 4], got {tuple(radial_coeffs.shape)}")
-        if radial_coeffs.shape[-1] == 4:
-            radial_coeffs = torch.nn.functional.pad(radial_coeffs, (0, 2))
-    if tangential_coeffs is not None and tangential_coeffs.shape != batch + (C, 2):
-        raise ValueError(f"tangential_coeffs must have shape [..., C, 2], got {tuple(tangential_coeffs.shape)}")
-    if thin_prism_coeffs is not None and thin_prism_coeffs.shape != batch + (C, 4):
-        raise ValueError(f"thin_prism_coeffs must have shape [..., C, 4], got {tuple(thin_prism_coeffs.shape)}")
-    if camera_model == 1 and (radial_coeffs is not None or tangential_coeffs is not None or thin_prism_coeffs is not None):
-        raise RuntimeError("ortho camera model does not support radial_coeffs, tangential_coeffs, or thin_prism_coeffs "
-                           "parameters")
-    alpha, beta, kappa, margin, all_valid = 0.1, 2.0, 0.0, 0.1, False  # Cameras.h:59-64
-    if ut_params is not None:
-        alpha, beta, kappa = float(ut_params.alpha), float(ut_params.beta), float(ut_params.kappa)
-        margin, all_valid = float(ut_params.in_image_margin_factor), bool(ut_params.require_all_sigma_points_valid)
-    dev, dt = means.device, means.dtype
-    radii = torch.empty(batch + (C, N, 2), device=dev, dtype=torch.int32)
-    means2d = torch.empty(batch + (C, N, 2), device=dev, dtype=dt)
-    depths = torch.empty(batch + (C, N), device=dev, dtype=dt)
-    conics = torch.empty(batch + (C, N, 3), device=dev, dtype=dt)
-    comps = torch.empty(batch + (C, N), device=dev, dtype=dt) if calc_compensations else None
-    if rolling or not global_z_order or external_distortion_params is not None:
-        import ctypes
-
-        if rolling and viewmats1.shape != viewmats0.shape:
-            raise ValueError("viewmats_rs must match viewmats shape")
-        head = (means.contiguous(), quats.contiguous(), scales.contiguous(),
-                _c(opacities), viewmats0.contiguous(), _c(viewmats1) if rolling else None, Ks.contiguous(),
-                _c(radial_coeffs), _c(tangential_coeffs), _c(thin_prism_coeffs), max_angle,
-                ctypes.addressof(ftheta_rec) if ftheta_rec is not None else None)
-        tail = (B, C, N, int(image_width), int(image_height),
-                float(eps2d), float(near_plane), float(far_plane), float(radius_clip), int(camera_model), int(rs_type),
-                int(bool(global_z_order)), alpha, beta, kappa, margin, int(all_valid), radii, means2d, depths,
-                conics, comps)
-        if external_distortion_params is not None:  # behind a windshield: sigma points go through the forward polynomials
-            ext = _windshield_record(external_distortion_params)
-            call("gsx_project_ut_ext_fwd", *head, ctypes.addressof(ext), *tail)
-        else:
-            call("gsx_project_ut_rs_fwd", *head, *tail)
-        return radii, means2d, depths, conics, comps
-    if ftheta_rec is not None:
-        import ctypes
-
-        call("gsx_project_ut_ftheta_fwd", means.contiguous(), quats.contiguous(), scales.contiguous(),
-             _c(opacities), viewmats0.contiguous(), Ks.contiguous(), ctypes.addressof(ftheta_rec), B, C, N,
-             int(image_width), int(image_height), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
-             alpha, beta, kappa, margin, int(all_valid), radii, means2d, depths, conics, comps)
-        return radii, means2d, depths, conics, comps
-    call("gsx_project_ut_fwd", means.contiguous(), quats.contiguous(), scales.contiguous(), _c(opacities),
-         viewmats0.contiguous(), Ks.contiguous(), _c(radial_coeffs), _c(tangential_coeffs), _c(thin_prism_coeffs), max_angle, B,
-         C, N, int(image_width), int(image_height), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
-         int(camera_model), alpha, beta, kappa, margin, int(all_valid), radii, means2d, depths, conics, comps)
-    return radii, means2d, depths, conics, comps
-
-
-def pinhole_pixel_rays(viewmats: Tensor, Ks: Tensor, width: int, height: int) -> Tensor:
-    """[..., C, H, W, 6]: world-space origin | unit direction of the ray through every pixel centre of perfect pinhole
-    cameras with a global shutter (what the reference's `_generate_rays` yields for that model,
-    gsplat/cuda/_torch_impl_eval3d.py:91-132): direction = R^T normalise(K^-1 (x + 0.5, y + 0.5, 1)), origin = -R^T t."""
-    dt, dev = viewmats.dtype, viewmats.device
-    xs = torch.arange(width, device=dev, dtype=dt) + 0.5
-    ys = torch.arange(height, device=dev, dtype=dt) + 0.5
-    fx, fy, cx, cy = (Ks[..., 0, 0, None, None], Ks[..., 1, 1, None, None], Ks[..., 0, 2, None, None],
-                      Ks[..., 1, 2, None, None])
-    dx = ((xs[None, :] - cx) / fx).expand(Ks.shape[:-2] + (height, width))
-    dy = ((ys[:, None] - cy) / fy).expand(Ks.shape[:-2] + (height, width))
-    d = torch.stack([dx, dy, torch.ones_like(dx)], dim=-1)
-    d = d / d.norm(dim=-1, keepdim=True)
-    R, t = viewmats[..., :3, :3], viewmats[..., :3, 3]
-    d_world = torch.einsum("...ji,...hwj->...hwi", R, d)
-    o_world = -torch.einsum("...ji,...j->...i", R, t)
-    return torch.cat([o_world[..., None, None, :].expand_as(d_world), d_world], dim=-1).contiguous()
-
-
-def _rotmat_to_quat_wxyz(R: Tensor) -> Tensor:
-    """glm::quat_cast of row-major rotation matrices [..., 3, 3] -> (w, x, y, z) (Cameras.cuh:85-101)."""
-    m = lambda i, j: R[..., i, j]  # noqa: E731
-    four = torch.stack([m(0, 0) + m(1, 1) + m(2, 2), m(0, 0) - m(1, 1) - m(2, 2), m(1, 1) - m(0, 0) - m(2, 2),
-                        m(2, 2) - m(0, 0) - m(1, 1)], dim=-1)
-    big = four.argmax(dim=-1)
-    val = torch.sqrt(four.gather(-1, big[..., None])[..., 0] + 1.0) * 0.5
-    mult = 0.25 / val
-    a, b, c = (m(2, 1) - m(1, 2)) * mult, (m(0, 2) - m(2, 0)) * mult, (m(1, 0) - m(0, 1)) * mult
-    d, e, f = (m(1, 0) + m(0, 1)) * mult, (m(0, 2) + m(2, 0)) * mult, (m(2, 1) + m(1, 2)) * mult
-    cands = torch.stack([torch.stack([val, a, b, c], -1), torch.stack([a, val, d, e], -1), torch.stack([b, d, val, f], -1),
-                         torch.stack([c, e, f, val], -1)], dim=-2)  # [..., case, 4]
-    return cands.gather(-2, big[..., None, None].expand(big.shape + (1, 4)))[..., 0, :]
-
-
-def _quat_rotate_wxyz(q: Tensor, v: Tensor) -> Tensor:
-    """glm::rotate(q, v) = v + 2 (w (u x v) + u x (u x v))."""
-    u = q[..., 1:]
-    uv = torch.cross(u, v, dim=-1)
-    return v + 2.0 * (q[..., :1] * uv + torch.cross(u, uv, dim=-1))
-
-
-def _slerp_wxyz(q0: Tensor, q1: Tensor, t: Tensor) -> Tensor:
-    """glm::slerp on the short arc (component-wise mix when nearly parallel), normalised (Cameras.cuh:362-429)."""
-    cos = (q0 * q1).sum(-1, keepdim=True)
-    q1 = torch.where(cos < 0, -q1, q1)
-    cos = cos.abs()
-    t = t[..., None]
-    angle = torch.acos(cos.clamp(max=1.0))
-    sin = torch.sin(angle)
-    safe = torch.where(sin > 0, sin, torch.ones_like(sin))
-    wa = torch.where(cos > 1.0 - 1.1920929e-07, 1.0 - t, torch.sin((1.0 - t) * angle) / safe)
-    wb = torch.where(cos > 1.0 - 1.1920929e-07, t, torch.sin(t * angle) / safe)
-    q = wa * q0 + wb * q1
-    return q / q.norm(dim=-1, keepdim=True)
-
-
-def pinhole_pixel_rays_rolling(viewmats: Tensor, viewmats_rs: Tensor, Ks: Tensor, width: int, height: int, rs_type: int) -> Tensor:
-    """pinhole_pixel_rays under a ROLLING shutter: the pose of a pixel is the one interpolated (translation lerp, rotation slerp)
-    at the relative frame time at which its row / column is read - floor(y) / (H - 1) top-to-bottom, floor(x) / (W - 1)
-    left-to-right, (H - ceil(y)) / (H - 1) bottom-to-top, (W - ceil(x)) / (W - 1) right-to-left at the pixel centre
-    (Cameras.cuh:503-546; gsplat/cuda/_torch_cameras.py:424-553). [..., C, H, W, 6]."""
-    dt, dev = viewmats.dtype, viewmats.device
-    xs = torch.arange(width, device=dev, dtype=dt) + 0.5
-    ys = torch.arange(height, device=dev, dtype=dt) + 0.5
-    if rs_type == 0:
-        tm, along_rows = (torch.floor(ys) / (height - 1) if height > 1 else torch.full_like(ys, 0.5)), True
-    elif rs_type == 2:
-        tm, along_rows = ((height - torch.ceil(ys)) / (height - 1) if height > 1 else torch.full_like(ys, 0.5)), True
-    elif rs_type == 1:
-        tm, along_rows = (torch.floor(xs) / (width - 1) if width > 1 else torch.full_like(xs, 0.5)), False
-    elif rs_type == 3:
-        tm, along_rows = ((width - torch.ceil(xs)) / (width - 1) if width > 1 else torch.full_like(xs, 0.5)), False
-    else:
-        raise ValueError(f"rolling shutter type {rs_type}")
-    L = tm.shape[0]
-    lead = viewmats.shape[:-2]
-    q0 = _rotmat_to_quat_wxyz(viewmats[..., :3, :3])[..., None, :].expand(lead + (L, 4))
-    q1 = _rotmat_to_quat_wxyz(viewmats_rs[..., :3, :3])[..., None, :].expand(lead + (L, 4))
-    t0, t1 = viewmats[..., None, :3, 3], viewmats_rs[..., None, :3, 3]
-    tl = tm.expand(lead + (L,))
-    q = _slerp_wxyz(q0, q1, tl)                                   # [..., C, L, 4] pose of every line
-    t = (1.0 - tl[..., None]) * t0 + tl[..., None] * t1           # [..., C, L, 3]
-    q_inv = torch.cat([q[..., :1], -q[..., 1:]], dim=-1)
-    origin = _quat_rotate_wxyz(q_inv, -t)                          # camera position at the line's time
-    fx, fy, cx, cy = (Ks[..., 0, 0, None, None], Ks[..., 1, 1, None, None], Ks[..., 0, 2, None, None],
-                      Ks[..., 1, 2, None, None])
-    dx = ((xs[None, :] - cx) / fx).expand(Ks.shape[:-2] + (height, width))
-    dy = ((ys[:, None] - cy) / fy).expand(Ks.shape[:-2] + (height, width))
-    d = torch.stack([dx, dy, torch.ones_like(dx)], dim=-1)
-    d = d / d.norm(dim=-1, keepdim=True)
-    if along_rows:
-        qi, oi = q_inv[..., :, None, :], origin[..., :, None, :]   # [..., C, H, 1, .]
-    else:
-        qi, oi = q_inv[..., None, :, :], origin[..., None, :, :]   # [..., C, 1, W, .]
-    d_world = _quat_rotate_wxyz(qi.expand(d.shape[:-1] + (4,)), d)
-    return torch.cat([oi.expand_as(d_world), d_world], dim=-1).contiguous()
-
-
 def _ftheta_record(ftheta_coeffs):
     """The 17-float host record the C-ABI takes for an f-theta camera: reference_poly | pixeldist_to_angle_poly[6] |
     angle_to_pixeldist_poly[6] | max_angle | linear_cde[3] (FThetaCameraDistortionParameters, Cameras.h:103-117)."""
-    import ctypes
-
     p2a, a2p = list(ftheta_coeffs.pixeldist_to_angle_poly), list(ftheta_coeffs.angle_to_pixeldist_poly)
     cde = list(ftheta_coeffs.linear_cde)
     if len(p2a) != 6 or len(a2p) != 6 or len(cde) != 3:
@@ -2035,8 +1839,6 @@ def _windshield_record(params):
     """The 84-float host record the C-ABI takes for the external (windshield) distortion: horizontal | vertical | horizontal
     inverse | vertical inverse polynomial of BivariateWindshieldModelParameters, each padded to the order-5 triangular layout of
     21 coefficients (block k = the coefficients in x of y^k; pad_coefficients_to_max_order, ExternalDistortion.cuh:104-124)."""
-    import ctypes
-
     def pad(t, what):
         vals = [float(v) for v in (t.detach().cpu().reshape(-1).tolist() if isinstance(t, Tensor) else list(t))]
         order = (-3 + int(math.sqrt(1 + 8 * len(vals)))) // 2  # compute_order
@@ -2055,17 +1857,97 @@ def _windshield_record(params):
     return (ctypes.c_float * 84)(*rec)
 
 
+def _camera_args(viewmats, viewmats_rs, Ks, width, height, camera_model, rs_type, radial_coeffs, tangential_coeffs,
+                 thin_prism_coeffs, ftheta_coeffs, external_distortion_params):
+    """A camera of model 0 .. 3 as gsx_project_ut_fwd and gsx_camera_rays take it, in entry order: (viewmats1, radial,
+    tangential, thin_prism, fisheye_max_angle, ftheta, ext). The one place that holds which coefficients a model takes. The two
+    host records are in the tuple as ctypes arrays, which keeps them alive until call() has returned."""
+    rolling = rs_type != ROLLING_SHUTTER_GLOBAL
+    if rolling and (viewmats_rs is None or viewmats_rs.shape != viewmats.shape):
+        raise ValueError("a rolling shutter needs viewmats_rs of the shape of viewmats")
+    has_opencv = radial_coeffs is not None or tangential_coeffs is not None or thin_prism_coeffs is not None
+    ftheta, max_angle = None, None
+    if camera_model == 3:  # f-theta: one parameter record per call, no OpenCV coefficients
+        if has_opencv:
+            raise ValueError("the f-theta camera model takes ftheta_coeffs, not radial / tangential / thin-prism coefficients")
+        if ftheta_coeffs is None:
+            raise ValueError("camera_model='ftheta' needs ftheta_coeffs (FThetaCameraDistortionParameters)")
+        ftheta = _ftheta_record(ftheta_coeffs)
+    if camera_model == 2:  # fisheye: k1..k4 only, plus the per-camera angle limit
+        if tangential_coeffs is not None or thin_prism_coeffs is not None:
+            raise ValueError("the fisheye camera model takes radial_coeffs [..., C, 4] only")
+        if radial_coeffs is None:
+            radial_coeffs = torch.zeros(tuple(viewmats.shape[:-2]) + (4,), device=viewmats.device, dtype=viewmats.dtype)
+        max_angle = fisheye_max_angle(radial_coeffs, Ks, int(width), int(height)).contiguous()
+    if camera_model == 1 and has_opencv:
+        raise RuntimeError("ortho camera model does not support radial_coeffs, tangential_coeffs, or thin_prism_coeffs "
+                           "parameters")
+    if radial_coeffs is not None and radial_coeffs.shape[-1] == 4:
+        radial_coeffs = torch.nn.functional.pad(radial_coeffs, (0, 2))
+    # behind a windshield the sigma points go through the forward polynomials, a generated ray through the inverse ones
+    ext = None if external_distortion_params is None else _windshield_record(external_distortion_params)
+    return (_c(viewmats_rs) if rolling else None, _c(radial_coeffs), _c(tangential_coeffs), _c(thin_prism_coeffs), max_angle,
+            ftheta, ext)
+
+
+@_op("projection_ut_3dgs_fused")
+def projection_ut_3dgs_fused(means, quats, scales, opacities, viewmats0, viewmats1, Ks, image_width, image_height,
+                             eps2d, near_plane, far_plane, radius_clip, calc_compensations, camera_model, global_z_order,
+                             ut_params, rs_type, radial_coeffs, tangential_coeffs, thin_prism_coeffs, ftheta_coeffs,
+                             lidar_coeffs, external_distortion_params):
+    """gsplat::projection_ut_3dgs_fused (kernel ``ProjectionUT3DGSFused.cu``): perfect / OpenCV pinhole, orthographic, OpenCV
+    fisheye, f-theta and spinning-lidar cameras, global or rolling shutter, z or Euclidean sort depth, with or without the
+    external (windshield) distortion. One kernel behind gsx_project_ut_fwd (models 0 .. 3) and gsx_project_ut_lidar_fwd."""
+    if rs_type != ROLLING_SHUTTER_GLOBAL and viewmats1 is None:
+        raise ValueError("a rolling shutter needs viewmats_rs (the pose at the end of the frame)")
+    if not 0 <= rs_type <= ROLLING_SHUTTER_GLOBAL:
+        raise ValueError(f"unknown rolling shutter type {rs_type}")
+    if camera_model not in CAMERA_MODEL_IDS.values():
+        raise NotImplementedError(f"gsplat_amd: UT projection is built for pinhole, ortho, fisheye, f-theta and lidar cameras, not "
+                                  f"'{camera_model}'")
+    if (camera_model == 4) != (lidar_coeffs is not None):
+        raise RuntimeError("Lidar coefficients must be given for lidar camera model" if camera_model == 4 else
+                           "lidar_coeffs given but camera_model is not lidar")
+    if camera_model == 4:
+        return _projection_ut_lidar(means, quats, scales, opacities, viewmats0, viewmats1, Ks, eps2d, near_plane, far_plane,
+                                    radius_clip, calc_compensations, global_z_order, ut_params, rs_type, lidar_coeffs,
+                                    radial_coeffs, tangential_coeffs, thin_prism_coeffs, external_distortion_params)
+    _check_f32(means=means, quats=quats, scales=scales, opacities=opacities, viewmats=viewmats0, viewmats_rs=viewmats1, Ks=Ks,
+               radial_coeffs=radial_coeffs, tangential_coeffs=tangential_coeffs, thin_prism_coeffs=thin_prism_coeffs)
+    batch = tuple(means.shape[:-2])
+    N, C, B = means.shape[-2], viewmats0.shape[-3], math.prod(batch)
+    if quats.shape != batch + (N, 4) or scales.shape != batch + (N, 3) or viewmats0.shape != batch + (C, 4, 4) \
+            or Ks.shape != batch + (C, 3, 3) or (opacities is not None and opacities.shape != batch + (N,)):
+        raise ValueError("projection_ut_3dgs_fused: inconsistent input shapes")
+    if rs_type != ROLLING_SHUTTER_GLOBAL and viewmats1.shape != viewmats0.shape:
+        raise ValueError("viewmats_rs must match viewmats shape")
+    if radial_coeffs is not None:
+        if camera_model == 2 and radial_coeffs.shape != batch + (C, 4):
+            raise ValueError(f"fisheye radial_coeffs must have shape [..., C, 4], got {tuple(radial_coeffs.shape)}")
+        if radial_coeffs.shape[:-1] != batch + (C,) or radial_coeffs.shape[-1] not in (4, 6):
+            raise ValueError(f"radial_coeffs must have shape [..., C, 6] or [..., C, 4], got {tuple(radial_coeffs.shape)}")
+    if tangential_coeffs is not None and tangential_coeffs.shape != batch + (C, 2):
+        raise ValueError(f"tangential_coeffs must have shape [..., C, 2], got {tuple(tangential_coeffs.shape)}")
+    if thin_prism_coeffs is not None and thin_prism_coeffs.shape != batch + (C, 4):
+        raise ValueError(f"thin_prism_coeffs must have shape [..., C, 4], got {tuple(thin_prism_coeffs.shape)}")
+    viewmats1, *coeffs = _camera_args(viewmats0, viewmats1, Ks, image_width, image_height, camera_model, rs_type, radial_coeffs,
+                                      tangential_coeffs, thin_prism_coeffs, ftheta_coeffs, external_distortion_params)
+    outs = _ut_outputs(means, batch + (C, N), calc_compensations)
+    call("gsx_project_ut_fwd", means.contiguous(), quats.contiguous(), scales.contiguous(), _c(opacities),
+         viewmats0.contiguous(), viewmats1, Ks.contiguous(), *coeffs, B, C, N, int(image_width), int(image_height), float(eps2d),
+         float(near_plane), float(far_plane), float(radius_clip), int(camera_model), int(rs_type), int(bool(global_z_order)),
+         *_ut_scalars(ut_params), *outs)
+    return outs
+
+
 @_op("distort_camera_rays")
 def distort_camera_rays(rays, horizontal_poly, vertical_poly, horizontal_poly_inverse, vertical_poly_inverse, reference_poly,
                         inverse):
     """gsplat::distort_camera_rays (ExternalDistortionWrappers.cu:96-160): the windshield model on rays [..., 3]; `inverse`
     applies the inverse pair of polynomials."""
-    import ctypes
-    import types as _types
-
     if rays.dtype != torch.float32 or rays.dim() < 1 or rays.shape[-1] != 3:
         raise RuntimeError("rays must be float32 with shape [..., 3]")
-    rec = _windshield_record(_types.SimpleNamespace(horizontal_poly=horizontal_poly, vertical_poly=vertical_poly,
+    rec = _windshield_record(types.SimpleNamespace(horizontal_poly=horizontal_poly, vertical_poly=vertical_poly,
                                                     horizontal_poly_inverse=horizontal_poly_inverse,
                                                     vertical_poly_inverse=vertical_poly_inverse))
     base = ctypes.addressof(rec)
@@ -2079,12 +1961,9 @@ def distort_camera_rays(rays, horizontal_poly, vertical_poly, horizontal_poly_in
 @_op("eval_bivariate_poly")
 def eval_bivariate_poly(x, y, poly_coeffs, order):
     """gsplat::eval_bivariate_poly (ExternalDistortionWrappers.cu:30-94)."""
-    import ctypes
-    import types as _types
-
     if x.dtype != torch.float32 or y.dtype != torch.float32 or x.numel() != y.numel():
         raise RuntimeError("x and y must be float32 tensors with the same number of elements")
-    one = _types.SimpleNamespace(horizontal_poly=poly_coeffs, vertical_poly=[0.0], horizontal_poly_inverse=[0.0],
+    one = types.SimpleNamespace(horizontal_poly=poly_coeffs, vertical_poly=[0.0], horizontal_poly_inverse=[0.0],
                                  vertical_poly_inverse=[0.0])
     rec = _windshield_record(one)
     x, y = x.contiguous(), y.contiguous()
@@ -2094,51 +1973,21 @@ def eval_bivariate_poly(x, y, poly_coeffs, order):
 
 
 def camera_pixel_rays(viewmats: Tensor, viewmats_rs: Optional[Tensor], Ks: Tensor, width: int, height: int, camera_model: int = 0,
-                      rs_type: int = 4, radial_coeffs: Optional[Tensor] = None,
+                      rs_type: int = ROLLING_SHUTTER_GLOBAL, radial_coeffs: Optional[Tensor] = None,
                       tangential_coeffs: Optional[Tensor] = None, thin_prism_coeffs: Optional[Tensor] = None,
                       ftheta_coeffs=None, external_distortion_params=None) -> Tensor:
     """[..., C, H, W, 6]: world-space origin | unit direction of the ray through every pixel centre, for every built camera model
     (perfect / OpenCV-distorted pinhole, orthographic, OpenCV fisheye, f-theta) under a global or rolling shutter - what the
     reference's from-world kernels derive per thread when no `rays` are passed (RasterizeToPixelsFromWorld3DGS.cuh:349-529).
     A pixel the model cannot invert gets the zero ray (no samples). One kernel: gsx_camera_rays (csrc/projection_ut.hip)."""
-    import ctypes
-
-    lead = tuple(viewmats.shape[:-2])
-    I = math.prod(lead)
-    dev, dt = viewmats.device, viewmats.dtype
-    rolling = rs_type != 4  # RollingShutterType.GLOBAL
-    if rolling and (viewmats_rs is None or viewmats_rs.shape != viewmats.shape):
-        raise ValueError("a rolling shutter needs viewmats_rs of the shape of viewmats")
-    ftheta_rec, max_angle = None, None
-    if camera_model == 3:
-        if ftheta_coeffs is None:
-            raise ValueError("camera_model='ftheta' needs ftheta_coeffs (FThetaCameraDistortionParameters)")
-        if radial_coeffs is not None or tangential_coeffs is not None or thin_prism_coeffs is not None:
-            raise ValueError("the f-theta camera model takes ftheta_coeffs, not radial / tangential / thin-prism coefficients")
-        ftheta_rec = _ftheta_record(ftheta_coeffs)
-    if camera_model == 2:
-        if tangential_coeffs is not None or thin_prism_coeffs is not None:
-            raise ValueError("the fisheye camera model takes radial_coeffs [..., C, 4] only")
-        if radial_coeffs is None:
-            radial_coeffs = torch.zeros(lead + (4,), device=dev, dtype=dt)
-        max_angle = fisheye_max_angle(radial_coeffs, Ks, int(width), int(height)).contiguous()
-    if camera_model == 1 and (radial_coeffs is not None or tangential_coeffs is not None or thin_prism_coeffs is not None):
-        raise RuntimeError("ortho camera model does not support radial_coeffs, tangential_coeffs, or thin_prism_coeffs "
-                           "parameters")
-    if radial_coeffs is not None and radial_coeffs.shape[-1] == 4:
-        radial_coeffs = torch.nn.functional.pad(radial_coeffs, (0, 2))
     _check_f32(viewmats=viewmats, viewmats_rs=viewmats_rs, Ks=Ks, radial_coeffs=radial_coeffs,
                tangential_coeffs=tangential_coeffs, thin_prism_coeffs=thin_prism_coeffs)
-    rays = torch.empty(lead + (int(height), int(width), 6), device=dev, dtype=dt)
-    head = (viewmats.contiguous(), _c(viewmats_rs) if rolling else None, Ks.contiguous(),
-            _c(radial_coeffs), _c(tangential_coeffs), _c(thin_prism_coeffs), max_angle,
-            ctypes.addressof(ftheta_rec) if ftheta_rec is not None else None)
-    tail = (I, int(width), int(height), int(camera_model), int(rs_type), rays)
-    if external_distortion_params is not None:  # behind a windshield: the camera model's ray goes through the inverse polynomials
-        ext = _windshield_record(external_distortion_params)
-        call("gsx_camera_rays_ext", *head, ctypes.addressof(ext), *tail)
-    else:
-        call("gsx_camera_rays", *head, *tail)
+    lead = tuple(viewmats.shape[:-2])
+    camera = _camera_args(viewmats, viewmats_rs, Ks, width, height, camera_model, rs_type, radial_coeffs, tangential_coeffs,
+                          thin_prism_coeffs, ftheta_coeffs, external_distortion_params)
+    rays = torch.empty(lead + (int(height), int(width), 6), device=viewmats.device, dtype=viewmats.dtype)
+    call("gsx_camera_rays", viewmats.contiguous(), camera[0], Ks.contiguous(), *camera[1:], math.prod(lead), int(width),
+         int(height), int(camera_model), int(rs_type), rays)
     return rays
 
 
@@ -2170,7 +2019,7 @@ class _FromWorldCompositing(torch.autograd.Function):
         off, fl = tile_offsets.contiguous(), flatten_ids.contiguous()
         counts = torch.empty(batch + (C, height, width), device=dev, dtype=torch.int32) if want_counts else None
         normals = torch.empty(batch + (C, height, width, 3), device=dev, dtype=dt) if want_normals else None
-        call("gsx_raster_world_fwd_ex", *args, bg, mk, off, fl, I, C, N, fl.numel(), D, int(width), int(height), int(tile_size),
+        call("gsx_raster_world_fwd", *args, bg, mk, off, fl, I, C, N, fl.numel(), D, int(width), int(height), int(tile_size),
              tw, th, int(bool(hit_distance)), renders, alphas, last_ids, counts, normals)
         ctx.save_for_backward(*args, off, fl, alphas, last_ids, *([bg] if bg is not None else []),
                               *([mk] if mk is not None else []))
@@ -2191,7 +2040,6 @@ class _FromWorldCompositing(torch.autograd.Function):
         has_bg, has_mk, I, C, N, D, width, height, tile_size, tw, th, batch = ctx.flags
         hit_distance, want_normals = ctx.extras
         want_rays = ctx.needs_input_grad[5]
-        extra = hit_distance or want_normals or want_rays
         saved = list(ctx.saved_tensors)
         means, quats, scales, colors, opacities, rays, off, fl, alphas, last_ids = saved[:10]
         rest = saved[10:]
@@ -2201,16 +2049,10 @@ class _FromWorldCompositing(torch.autograd.Function):
         rows = torch.zeros((I * N, width_rows), device=means.device, dtype=means.dtype)
         v_r = (torch.zeros_like(alphas).expand(alphas.shape[:-1] + (D,)) if v_renders is None else v_renders).contiguous()
         v_a = None if v_alphas is None else v_alphas.contiguous()
-        v_rays = None
-        if extra:
-            v_n = None if (v_normals is None or not want_normals) else v_normals.contiguous()
-            v_rays = torch.zeros(ctx.rays_shape, device=means.device, dtype=means.dtype) if want_rays else None
-            call("gsx_raster_world_bwd_ex", means, quats, scales, colors, opacities, rays, bg,
-                 mk, off, fl, alphas, last_ids, v_r, v_a, v_n, I, C, N, fl.numel(), D,
-                 width, height, tile_size, tw, th, int(hit_distance), rows, width_rows, v_rays)
-        else:
-            call("gsx_raster_world_bwd", means, quats, scales, colors, opacities, rays, bg, mk, off, fl, alphas, last_ids, v_r,
-                 v_a, I, C, N, fl.numel(), D, width, height, tile_size, tw, th, rows, width_rows)
+        v_n = None if (v_normals is None or not want_normals) else v_normals.contiguous()
+        v_rays = torch.zeros(ctx.rays_shape, device=means.device, dtype=means.dtype) if want_rays else None
+        call("gsx_raster_world_bwd", means, quats, scales, colors, opacities, rays, bg, mk, off, fl, alphas, last_ids, v_r, v_a,
+             v_n, I, C, N, fl.numel(), D, width, height, tile_size, tw, th, int(hit_distance), rows, width_rows, v_rays)
         B = I // C
         per = rows.view(B, C, N, width_rows)
         v_means = per[..., 0:3].sum(1).reshape(means.shape)
@@ -2293,13 +2135,13 @@ def rasterize_to_pixels_from_world_3dgs(means, quats, scales, colors, opacities,
                                         return_last_ids, unsafe_masked_tile_outputs=False):
     """gsplat::rasterize_to_pixels_from_world_3dgs (forward + autograd, like the reference's C++ autograd function,
     Rasterization.cpp:3266-3340): dense rows, rays either given or generated for every built camera model (global or rolling
-    shutter: camera_pixel_rays), sample counts, hit distance, normals, gradients to the rays and the backgrounds. Lidar and
-    external distortion are refused, never approximated."""
+    shutter, behind a windshield or not: camera_pixel_rays; a spinning lidar's elements: lidar_element_rays), sample counts, hit
+    distance, normals, gradients to the rays and the backgrounds."""
     if renderer_config not in (0, 1):
         raise ValueError(f"unknown renderer_config {renderer_config}")
     # renderer_config 1 (PARALLEL_BATCH, Rasterization.cpp:106-117) is a scheduling choice of the reference (its lists split over
     # several CTAs); this backend has one schedule, the results are the same
-    rolling = rs_type != _ROLLING_SHUTTER_GLOBAL
+    rolling = rs_type != ROLLING_SHUTTER_GLOBAL
     if rolling and viewmats1 is None:
         raise ValueError("a rolling shutter needs viewmats_rs (the pose at the end of the frame)")
     if (camera_model == 4) != (lidar_coeffs is not None):
@@ -2311,7 +2153,7 @@ def rasterize_to_pixels_from_world_3dgs(means, quats, scales, colors, opacities,
     if rays is None:
         if camera_model not in (0, 1, 2, 3):
             raise NotImplementedError(f"gsplat_amd: eval3d generates rays for pinhole, ortho, fisheye and f-theta cameras, not "
-                                      f"'{_CAMERA_MODEL_NAMES.get(camera_model, camera_model)}'")
+                                      f"'{camera_model}'")
         with torch.no_grad():  # the pose of a pixel is the one at the time its row / column is read
             rays = camera_pixel_rays(viewmats0, viewmats1 if rolling else None, Ks, int(image_width), int(image_height),
                                      int(camera_model), int(rs_type), radial_coeffs, tangential_coeffs, thin_prism_coeffs,
@@ -2336,8 +2178,6 @@ def rasterize_to_pixels_from_world_3dgs(means, quats, scales, colors, opacities,
 # ----------------------------------------------------------------------------------------------
 # whole-pipeline ops (what the reference's gsplat.rasterization() / rasterization_2dgs() call)
 # ----------------------------------------------------------------------------------------------
-_CAMERA_MODEL_NAMES = {0: "pinhole", 1: "ortho", 2: "fisheye", 3: "ftheta", 4: "lidar"}  # Common.h:75-82
-_ROLLING_SHUTTER_GLOBAL = 4  # _wrapper.py RollingShutterType.GLOBAL
 _SELF_DIFFERENTIABLE = ("rasterize_to_pixels_from_world_3dgs",)
 
 
@@ -2363,7 +2203,7 @@ def rasterization_3dgs(means, covars, quats, scales, opacities, colors, viewmats
     if renderer_config != 0 and not with_eval3d:
         raise ValueError("RendererConfig PARALLEL_BATCH requires with_eval3d=True; the classic path only supports "
                          "MIXED_BATCH")
-    if camera_model not in _CAMERA_MODEL_NAMES:
+    if camera_model not in CAMERA_MODEL_IDS.values():
         raise ValueError(f"unknown camera_model id {camera_model}")
     depth = ""
     if append_depth or use_hit_distance:
@@ -2378,7 +2218,7 @@ def rasterization_3dgs(means, covars, quats, scales, opacities, colors, viewmats
         sh_degree=None if sh_degree < 0 else sh_degree, packed=packed, tile_size=tile_size, backgrounds=backgrounds,
         render_mode=render_mode, sparse_grad=sparse_grad, absgrad=absgrad,
         rasterize_mode="antialiased" if calc_compensations else "classic", channel_chunk=channel_chunk,
-        distributed=process_group_name is not None or world_size > 1, camera_model=_CAMERA_MODEL_NAMES[camera_model],
+        distributed=process_group_name is not None or world_size > 1, camera_model=list(CAMERA_MODEL_IDS)[camera_model],
         segmented=segmented, covars=covars, with_ut=with_ut, with_eval3d=with_eval3d, return_normals=return_normals,
         global_z_order=global_z_order, rays=rays, radial_coeffs=radial_coeffs, tangential_coeffs=tangential_coeffs,
         thin_prism_coeffs=thin_prism_coeffs, ftheta_coeffs=ftheta_coeffs if camera_model == 3 else None,

@@ -70,22 +70,22 @@ def fully_fused_projection_with_ut(
     ftheta_coeffs=None,
     lidar_coeffs=None,
     external_distortion_coeffs=None,
-    rolling_shutter: int = 4,  # RollingShutterType.GLOBAL
+    rolling_shutter: int = _impl.ROLLING_SHUTTER_GLOBAL,
     viewmats_rs: Optional[Tensor] = None,
     global_z_order: bool = True,
 ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Optional[Tensor]]:
     """Projects Gaussians to 2D with the Unscented Transform — like ``fully_fused_projection`` but through a camera model
     with lens distortion; not differentiable (reference ``gsplat/cuda/_wrapper.py:2545-2633``). Returns
-    (radii [..., C, N, 2], means2d, depths, conics, compensations or None). Built: pinhole (perfect or OpenCV-distorted)
-    and ortho cameras with a global shutter."""
-    models = {"pinhole": 0, "ortho": 1, "fisheye": 2, "ftheta": 3, "lidar": 4}
-    if camera_model not in models:
+    (radii [..., C, N, 2], means2d, depths, conics, compensations or None). Built: pinhole (perfect or OpenCV-distorted),
+    ortho, OpenCV fisheye, f-theta and spinning-lidar cameras, with a global or a rolling shutter, the z or the Euclidean sort
+    depth, and the external (windshield) distortion."""
+    if camera_model not in _impl.CAMERA_MODEL_IDS:
         raise ValueError(f"unknown camera_model '{camera_model}'")
     c = lambda t: None if t is None else t.contiguous()  # noqa: E731
     return _ops.projection_ut_3dgs_fused(
         means.contiguous(), quats.contiguous(), scales.contiguous(), c(opacities), viewmats.contiguous(), c(viewmats_rs),
         Ks.contiguous(), width, height, eps2d, near_plane, far_plane, radius_clip, calc_compensations,
-        models[camera_model], global_z_order, ut_params, int(rolling_shutter), c(radial_coeffs), c(tangential_coeffs),
+        _impl.CAMERA_MODEL_IDS[camera_model], global_z_order, ut_params, int(rolling_shutter), c(radial_coeffs), c(tangential_coeffs),
         c(thin_prism_coeffs), ftheta_coeffs, lidar_coeffs, external_distortion_coeffs)
 
 
@@ -113,46 +113,40 @@ def rasterize_to_pixels_eval3d(
     ftheta_coeffs=None,
     lidar_coeffs=None,
     external_distortion_coeffs=None,
-    rolling_shutter: int = 4,
+    rolling_shutter: int = _impl.ROLLING_SHUTTER_GLOBAL,
     viewmats_rs: Optional[Tensor] = None,
     use_hit_distance: bool = False,
     return_normals: bool = False,
     renderer_config=None,
 ) -> Tuple[Tensor, Tensor]:
     """Like ``rasterize_to_pixels`` but every sample is the Gaussian's response along the pixel's ray in world space
-    (reference ``gsplat/cuda/_wrapper.py:2263-2353``): perfect pinhole cameras or caller-provided ``rays``, global
-    shutter. Differentiable w.r.t. means / quats / scales / colors / opacities and - where they require grad - the caller's
-    ``rays`` (v_rays) and ``backgrounds`` (v_backgrounds); the cameras are constants (reference kernel
-    RasterizeToPixelsFromWorld3DGSBwd.cu). Returns (render_colors, render_alphas)."""
-    models = {"pinhole": 0, "ortho": 1, "fisheye": 2, "ftheta": 3, "lidar": 4}
-    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
-    cls = torch.classes.gsplat
-    out = _ops.rasterize_to_pixels_from_world_3dgs(
-        means.contiguous(), quats.contiguous(), scales.contiguous(), colors.contiguous(), opacities.contiguous(),
-        c(backgrounds), c(masks), image_width, image_height, tile_size, viewmats.contiguous(), c(viewmats_rs),
-        Ks.contiguous(), models[camera_model], ut_params if ut_params is not None else cls.UnscentedTransformParameters(),
-        int(rolling_shutter), c(rays), c(radial_coeffs), c(tangential_coeffs), c(thin_prism_coeffs),
-        ftheta_coeffs if ftheta_coeffs is not None else cls.FThetaCameraDistortionParameters(), lidar_coeffs,
-        external_distortion_coeffs, isect_offsets.contiguous(), flatten_ids.contiguous(), False, use_hit_distance,
-        return_normals, 0 if renderer_config is None else int(renderer_config), False)
-    return out[0], out[1]
+    (reference ``gsplat/cuda/_wrapper.py:2263-2353``): caller-provided ``rays``, or rays generated for the camera model
+    (pinhole, ortho, fisheye, f-theta, spinning lidar; global or rolling shutter; behind a windshield or not). Differentiable
+    w.r.t. means / quats / scales / colors / opacities and - where they require grad - the caller's ``rays`` (v_rays) and
+    ``backgrounds`` (v_backgrounds); the cameras are constants (reference kernel RasterizeToPixelsFromWorld3DGSBwd.cu).
+    Returns (render_colors, render_alphas)."""
+    return rasterize_to_pixels_eval3d_extra(
+        means, quats, scales, colors, opacities, viewmats, Ks, image_width, image_height, tile_size, isect_offsets, flatten_ids,
+        backgrounds, masks, camera_model, ut_params, rays, radial_coeffs, tangential_coeffs, thin_prism_coeffs, ftheta_coeffs,
+        lidar_coeffs, external_distortion_coeffs, rolling_shutter, viewmats_rs, use_hit_distance=use_hit_distance,
+        return_normals=return_normals, renderer_config=renderer_config, return_last_ids=False)[:2]
 
 
 def rasterize_to_pixels_eval3d_extra(means, quats, scales, colors, opacities, viewmats, Ks, image_width, image_height, tile_size,
                                      isect_offsets, flatten_ids, backgrounds=None, masks=None, camera_model="pinhole",
                                      ut_params=None, rays=None, radial_coeffs=None, tangential_coeffs=None, thin_prism_coeffs=None,
-                                     ftheta_coeffs=None, lidar_coeffs=None, external_distortion_coeffs=None, rolling_shutter=4,
+                                     ftheta_coeffs=None, lidar_coeffs=None, external_distortion_coeffs=None,
+                                     rolling_shutter=_impl.ROLLING_SHUTTER_GLOBAL,
                                      viewmats_rs=None, return_sample_counts=False, use_hit_distance=False, return_normals=False,
                                      renderer_config=None, return_last_ids=True):
     """rasterize_to_pixels_eval3d + the optional outputs (reference ``gsplat/cuda/_wrapper.py:2356-2482``): returns
     (render_colors, render_alphas, last_ids or None, sample_counts or None, render_normals or None)."""
-    models = {"pinhole": 0, "ortho": 1, "fisheye": 2, "ftheta": 3, "lidar": 4}
     c = lambda t: None if t is None else t.contiguous()  # noqa: E731
     cls = torch.classes.gsplat
     return _ops.rasterize_to_pixels_from_world_3dgs(
         means.contiguous(), quats.contiguous(), scales.contiguous(), colors.contiguous(), opacities.contiguous(),
         c(backgrounds), c(masks), image_width, image_height, tile_size, viewmats.contiguous(), c(viewmats_rs),
-        Ks.contiguous(), models[camera_model], ut_params if ut_params is not None else cls.UnscentedTransformParameters(),
+        Ks.contiguous(), _impl.CAMERA_MODEL_IDS[camera_model], ut_params if ut_params is not None else cls.UnscentedTransformParameters(),
         int(rolling_shutter), c(rays), c(radial_coeffs), c(tangential_coeffs), c(thin_prism_coeffs),
         ftheta_coeffs if ftheta_coeffs is not None else cls.FThetaCameraDistortionParameters(), lidar_coeffs,
         external_distortion_coeffs, isect_offsets.contiguous(), flatten_ids.contiguous(), bool(return_sample_counts),

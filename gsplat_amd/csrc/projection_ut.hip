@@ -12,12 +12,12 @@
 //      first invalid point;
 //   4. blur + compensation, determinant / diagonal checks, conic = inverse (of cov + 1e-6 I, like the reference),
 //      opacity-aware extent, eigenvalue-bounded radii, radius clip, image-bounds cull. Invalid rows are zero.
-// Built so far: camera_model 0 (pinhole, with optional radial[6] / tangential[2] / thin-prism[4] coefficients),
+// Built: camera_model 0 (pinhole, with optional radial[6] / tangential[2] / thin-prism[4] coefficients),
 // 1 (orthographic), 2 (OpenCV fisheye, _torch_cameras.py:1335-1697: k1..k4 in radial[0..3]; the largest angle the
-// model projects is a per-camera quantity computed by the caller) and 3 (f-theta, _torch_cameras.py FThetaCamera:
+// model projects is a per-camera quantity computed by the caller), 3 (f-theta, _torch_cameras.py FThetaCamera:
 // pixel distance = polynomial of the ray angle, either polynomial direction as the calibrated one, linear (c, d, e) sensor map,
-// principal point shifted by half a pixel; gsx_project_ut_ftheta_fwd), global shutter. Lidar, rolling shutter and the
-// windshield model are rejected.
+// principal point shifted by half a pixel) and 4 (spinning lidar, gsx_project_ut_lidar_fwd), each under a global or a rolling
+// shutter; 0 .. 3 behind the windshield model or not. The same file generates rays: gsx_camera_rays, gsx_lidar_rays.
 #include "projmath.hpp"
 #include "../../include/gsplat_amd.h"
 
@@ -688,37 +688,49 @@ static void set_lidar(gsx::ProjUtArgs &a, const LidarHost *l)
     a.ld_ccw = l->ccw ? 1 : 0; a.ld_map = l->map; a.ld_map_h = l->map_h; a.ld_map_w = l->map_w; a.ld_columns = l->n_columns;
 }
 
-static int project_ut_launch(const float *means, const float *quats, const float *scales, const float *opacities,
-                             const float *viewmats, const float *Ks, const float *radial, const float *tangential,
-                             const float *thin_prism, const float *fisheye_max_angle, const float *ftheta, uint32_t B, uint32_t C,
-                             uint32_t N, uint32_t width, uint32_t height, float eps2d, float near_plane, float far_plane,
-                             float radius_clip, int camera_model, float ut_alpha, float ut_beta, float ut_kappa,
+// `ftheta`: HOST array of 17 floats - reference_poly (0 / 1), pixeldist_to_angle_poly[6], angle_to_pixeldist_poly[6], max_angle,
+// linear_cde[3] (the fields of FThetaCameraDistortionParameters, Cameras.h:103-117); read for camera_model 3 only
+static void set_ftheta(gsx::ProjUtArgs &a, const float *ftheta)
+{
+    if (a.camera_model != 3) return;
+    a.ft_reference_poly = ftheta[0] != 0.0f ? 1 : 0;
+    for (int i = 0; i < 6; ++i) { a.ft_p2a[i] = ftheta[1 + i]; a.ft_a2p[i] = ftheta[7 + i]; }
+    a.ft_max_angle = ftheta[13]; a.ft_c = ftheta[14]; a.ft_d = ftheta[15]; a.ft_e = ftheta[16];
+}
+
+// The one body of the projection entries: `fn` = the entry that was called (its name leads every message); `lidar` non-NULL
+// exactly for camera_model 4 (gsx_project_ut_lidar_fwd)
+static int project_ut_launch(const char *fn, const float *means, const float *quats, const float *scales, const float *opacities,
+                             const float *viewmats, const float *viewmats1, const float *Ks, const float *radial,
+                             const float *tangential, const float *thin_prism, const float *fisheye_max_angle, const float *ftheta,
+                             const float *ext, const LidarHost *lidar, uint32_t B, uint32_t C, uint32_t N, uint32_t width,
+                             uint32_t height, float eps2d, float near_plane, float far_plane, float radius_clip, int camera_model,
+                             int rs_type, int global_z_order, float ut_alpha, float ut_beta, float ut_kappa,
                              float in_image_margin_factor, int require_all_sigma_points_valid, int32_t *radii, float *means2d,
-                             float *depths, float *conics, float *compensations, void *stream, const float *viewmats1 = nullptr,
-                             int rs_type = 4, int global_z_order = 1, const float *ext = nullptr, const LidarHost *lidar = nullptr)
+                             float *depths, float *conics, float *compensations, void *stream)
 {
     using namespace gsx;
-    GSX_REQUIRE(rs_type >= 0 && rs_type <= 4, "gsx_project_ut_rs_fwd: rolling shutter type %d (0 .. 3 rolling, 4 global)", rs_type);
-    GSX_REQUIRE(rs_type == 4 || viewmats1 != nullptr, "gsx_project_ut_rs_fwd: a rolling shutter needs the end-of-frame poses");
+    GSX_REQUIRE(rs_type >= 0 && rs_type <= 4, "%s: rolling shutter type %d (0 .. 3 rolling, 4 global)", fn, rs_type);
+    GSX_REQUIRE(rs_type == 4 || viewmats1 != nullptr, "%s: a rolling shutter needs the end-of-frame poses", fn);
     const int64_t rows = (int64_t)B * C * N;
     if (rows == 0) return GSX_OK;
-    GSX_REQUIRE(means && quats && scales && viewmats && Ks, "gsx_project_ut_fwd: null input");
-    GSX_REQUIRE(radii && means2d && depths && conics, "gsx_project_ut_fwd: null output");
+    GSX_REQUIRE(means && quats && scales && viewmats && Ks, "%s: null input", fn);
+    GSX_REQUIRE(radii && means2d && depths && conics, "%s: null output", fn);
     GSX_REQUIRE(camera_model >= 0 && camera_model <= 4,
-                "gsx_project_ut_fwd: camera model %d is not built (pinhole = 0, orthographic = 1, fisheye = 2, f-theta = 3, lidar = 4 are)",
+                "%s: camera model %d is not built (pinhole = 0, orthographic = 1, fisheye = 2, f-theta = 3, lidar = 4 are)", fn,
                 camera_model);
-    GSX_REQUIRE((camera_model == 4) == (lidar != nullptr), "gsx_project_ut_fwd: the lidar model (4) goes through gsx_project_ut_lidar_fwd");
-    GSX_REQUIRE(camera_model != 4 || (!radial && !tangential && !thin_prism && !ext), "gsx_project_ut_lidar_fwd: a lidar takes no distortion coefficients");
+    GSX_REQUIRE((camera_model == 4) == (lidar != nullptr), "%s: the lidar model (4) goes through gsx_project_ut_lidar_fwd", fn);
+    GSX_REQUIRE(camera_model != 4 || (!radial && !tangential && !thin_prism && !ext), "%s: a lidar takes no distortion coefficients", fn);
     GSX_REQUIRE(camera_model != 4 || rs_type == 4 || (lidar->map && lidar->map_h > 1 && lidar->map_w > 1 && lidar->n_columns > 1),
-                "gsx_project_ut_lidar_fwd: a rolling shutter needs the angles_to_columns_map");
+                "%s: a rolling shutter needs the angles_to_columns_map", fn);
     GSX_REQUIRE(camera_model != 1 || (!radial && !tangential && !thin_prism),
-                "gsx_project_ut_fwd: the orthographic model takes no distortion coefficients");
+                "%s: the orthographic model takes no distortion coefficients", fn);
     GSX_REQUIRE(camera_model != 2 || (fisheye_max_angle && !tangential && !thin_prism),
-                "gsx_project_ut_fwd: the fisheye model needs fisheye_max_angle and takes radial coefficients only");
+                "%s: the fisheye model needs fisheye_max_angle and takes radial coefficients only", fn);
     GSX_REQUIRE(camera_model != 3 || (ftheta && !radial && !tangential && !thin_prism),
-                "gsx_project_ut_ftheta_fwd: the f-theta model needs its parameter record and takes no other coefficients");
+                "%s: the f-theta model needs its parameter record and takes no other coefficients", fn);
     const double lam = (double)ut_alpha * ut_alpha * (3.0 + ut_kappa) - 3.0;
-    GSX_REQUIRE(3.0 + lam > 0.0, "gsx_project_ut_fwd: alpha^2 (3 + kappa) must be positive");
+    GSX_REQUIRE(3.0 + lam > 0.0, "%s: alpha^2 (3 + kappa) must be positive", fn);
     ProjUtArgs a{};
     a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.viewmats = viewmats; a.Ks = Ks;
     a.radial = radial; a.tangential = tangential; a.thin_prism = thin_prism; a.max_angle = fisheye_max_angle;
@@ -726,11 +738,7 @@ static int project_ut_launch(const float *means, const float *quats, const float
     a.eps2d = eps2d; a.near_plane = near_plane; a.far_plane = far_plane; a.radius_clip = radius_clip;
     a.camera_model = camera_model; a.require_all_valid = require_all_sigma_points_valid;
     a.distorted = (radial || tangential || thin_prism) ? 1 : 0;
-    if (camera_model == 3) {
-        a.ft_reference_poly = ftheta[0] != 0.0f ? 1 : 0;
-        for (int i = 0; i < 6; ++i) { a.ft_p2a[i] = ftheta[1 + i]; a.ft_a2p[i] = ftheta[7 + i]; }
-        a.ft_max_angle = ftheta[13]; a.ft_c = ftheta[14]; a.ft_d = ftheta[15]; a.ft_e = ftheta[16];
-    }
+    set_ftheta(a, ftheta);
     a.w_m0 = (float)(lam / (3.0 + lam));
     a.w_c0 = (float)(lam / (3.0 + lam) + (1.0 - (double)ut_alpha * ut_alpha + ut_beta));
     a.w_i  = (float)(1.0 / (2.0 * (3.0 + lam)));
@@ -746,64 +754,36 @@ static int project_ut_launch(const float *means, const float *quats, const float
     return check_launch("project_ut_fwd");
 }
 
+// Camera models 0 .. 3, global or rolling shutter, z or Euclidean sort depth, with or without a windshield (contract:
+// include/gsplat_amd.h)
 extern "C" int gsx_project_ut_fwd(const float *means, const float *quats, const float *scales, const float *opacities,
-                                  const float *viewmats, const float *Ks, const float *radial, const float *tangential,
-                                  const float *thin_prism, const float *fisheye_max_angle, uint32_t B, uint32_t C, uint32_t N, uint32_t width,
+                                  const float *viewmats0, const float *viewmats1, const float *Ks, const float *radial,
+                                  const float *tangential, const float *thin_prism, const float *fisheye_max_angle,
+                                  const float *ftheta, const float *ext, uint32_t B, uint32_t C, uint32_t N, uint32_t width,
                                   uint32_t height, float eps2d, float near_plane, float far_plane, float radius_clip,
-                                  int camera_model, float ut_alpha, float ut_beta, float ut_kappa,
-                                  float in_image_margin_factor, int require_all_sigma_points_valid, int32_t *radii,
-                                  float *means2d, float *depths, float *conics, float *compensations, void *stream)
+                                  int camera_model, int rs_type, int global_z_order, float ut_alpha, float ut_beta,
+                                  float ut_kappa, float in_image_margin_factor, int require_all_sigma_points_valid,
+                                  int32_t *radii, float *means2d, float *depths, float *conics, float *compensations,
+                                  void *stream)
 {
-    GSX_REQUIRE(camera_model != 3, "gsx_project_ut_fwd: the f-theta model takes its parameters through gsx_project_ut_ftheta_fwd");
-    return project_ut_launch(means, quats, scales, opacities, viewmats, Ks, radial, tangential, thin_prism, fisheye_max_angle, nullptr,
-                             B, C, N, width, height, eps2d, near_plane, far_plane, radius_clip, camera_model, ut_alpha, ut_beta,
-                             ut_kappa, in_image_margin_factor, require_all_sigma_points_valid, radii, means2d, depths, conics,
+    return project_ut_launch("gsx_project_ut_fwd", means, quats, scales, opacities, viewmats0, viewmats1, Ks, radial, tangential,
+                             thin_prism, fisheye_max_angle, ftheta, ext, nullptr, B, C, N, width, height, eps2d, near_plane,
+                             far_plane, radius_clip, camera_model, rs_type, global_z_order, ut_alpha, ut_beta, ut_kappa,
+                             in_image_margin_factor, require_all_sigma_points_valid, radii, means2d, depths, conics,
                              compensations, stream);
-}
-
-// f-theta cameras: `ftheta` is a HOST array of 17 floats - reference_poly (0 / 1), pixeldist_to_angle_poly[6],
-// angle_to_pixeldist_poly[6], max_angle, linear_cde[3] (the fields of FThetaCameraDistortionParameters, Cameras.h:103-117)
-extern "C" int gsx_project_ut_ftheta_fwd(const float *means, const float *quats, const float *scales, const float *opacities,
-                                         const float *viewmats, const float *Ks, const float *ftheta, uint32_t B, uint32_t C,
-                                         uint32_t N, uint32_t width, uint32_t height, float eps2d, float near_plane, float far_plane,
-                                         float radius_clip, float ut_alpha, float ut_beta, float ut_kappa,
-                                         float in_image_margin_factor, int require_all_sigma_points_valid, int32_t *radii,
-                                         float *means2d, float *depths, float *conics, float *compensations, void *stream)
-{
-    GSX_REQUIRE(ftheta != nullptr, "gsx_project_ut_ftheta_fwd: null parameter record");
-    return project_ut_launch(means, quats, scales, opacities, viewmats, Ks, nullptr, nullptr, nullptr, nullptr, ftheta, B, C, N,
-                             width, height, eps2d, near_plane, far_plane, radius_clip, 3, ut_alpha, ut_beta, ut_kappa,
-                             in_image_margin_factor, require_all_sigma_points_valid, radii, means2d, depths, conics, compensations,
-                             stream);
-}
-
-// Every camera model of the two entries above + rolling shutter + the Euclidean sort depth, one entry: `viewmats1` = pose at the
-// end of the frame (NULL with rs_type 4 = global), `rs_type` as Cameras.h:38-45, `global_z_order` 0 = depths are |mean_c| (and
-// f-theta cameras cull near / far radially). `ftheta` = the 17-float host record of gsx_project_ut_ftheta_fwd or NULL.
-extern "C" int gsx_project_ut_rs_fwd(const float *means, const float *quats, const float *scales, const float *opacities,
-                                     const float *viewmats0, const float *viewmats1, const float *Ks, const float *radial,
-                                     const float *tangential, const float *thin_prism, const float *fisheye_max_angle,
-                                     const float *ftheta, uint32_t B, uint32_t C, uint32_t N, uint32_t width, uint32_t height,
-                                     float eps2d, float near_plane, float far_plane, float radius_clip, int camera_model,
-                                     int rs_type, int global_z_order, float ut_alpha, float ut_beta, float ut_kappa,
-                                     float in_image_margin_factor, int require_all_sigma_points_valid, int32_t *radii,
-                                     float *means2d, float *depths, float *conics, float *compensations, void *stream)
-{
-    return project_ut_launch(means, quats, scales, opacities, viewmats0, Ks, radial, tangential, thin_prism, fisheye_max_angle, ftheta,
-                             B, C, N, width, height, eps2d, near_plane, far_plane, radius_clip, camera_model, ut_alpha, ut_beta,
-                             ut_kappa, in_image_margin_factor, require_all_sigma_points_valid, radii, means2d, depths, conics,
-                             compensations, stream, viewmats1, rs_type, global_z_order);
 }
 
 // Rays of every pixel of I images, [I,H,W,6] = world-space origin | unit direction (the zero ray where the camera model cannot
 // invert the pixel): what the reference's from-world rasterizer derives per thread when no `rays` tensor is passed
 // (compute_world_ray, RasterizeToPixelsFromWorld3DGS.cuh:349-529; BaseCameraModel::element_to_world_ray_shutter_pose,
-// Cameras.cuh:503-546). viewmats_rs NULL / rs_type 4 = global shutter; coefficients as in gsx_project_ut_rs_fwd, one record per
-// image (radial [I,6], tangential [I,2], thin_prism [I,4], fisheye_max_angle [I]); `ftheta` the 17-float HOST record.
-static int camera_rays_impl(const float *viewmats, const float *viewmats_rs, const float *Ks, const float *radial,
-                            const float *tangential, const float *thin_prism, const float *fisheye_max_angle,
-                            const float *ftheta, const float *ext, uint32_t n_images, uint32_t width, uint32_t height,
-                            int camera_model, int rs_type, float *rays, void *stream)
+// Cameras.cuh:503-546). viewmats_rs NULL / rs_type 4 = global shutter; coefficients as in gsx_project_ut_fwd, one record per
+// image (radial [I,6], tangential [I,2], thin_prism [I,4], fisheye_max_angle [I]); `ftheta` the 17-float HOST record; `ext` the
+// 84-float windshield record, through whose INVERSE polynomials the camera model's ray is taken
+// (BaseCameraModel::image_point_to_camera_ray, Cameras.cuh:473-484), or NULL.
+extern "C" int gsx_camera_rays(const float *viewmats, const float *viewmats_rs, const float *Ks, const float *radial,
+                               const float *tangential, const float *thin_prism, const float *fisheye_max_angle,
+                               const float *ftheta, const float *ext, uint32_t n_images, uint32_t width, uint32_t height,
+                               int camera_model, int rs_type, float *rays, void *stream)
 {
     using namespace gsx;
     const int64_t n = (int64_t)n_images * width * height;
@@ -821,52 +801,11 @@ static int camera_rays_impl(const float *viewmats, const float *viewmats_rs, con
     a.radial = radial; a.tangential = tangential; a.thin_prism = thin_prism; a.max_angle = fisheye_max_angle;
     a.width = width; a.height = height; a.camera_model = camera_model; a.rs_type = rs_type;
     a.distorted = (radial || tangential || thin_prism) ? 1 : 0;
-    if (camera_model == 3) {
-        a.ft_reference_poly = ftheta[0] != 0.0f ? 1 : 0;
-        for (int i = 0; i < 6; ++i) { a.ft_p2a[i] = ftheta[1 + i]; a.ft_a2p[i] = ftheta[7 + i]; }
-        a.ft_max_angle = ftheta[13]; a.ft_c = ftheta[14]; a.ft_d = ftheta[15]; a.ft_e = ftheta[16];
-    }
+    set_ftheta(a, ftheta);
     set_external_distortion(a, ext);
     g.n_images = n_images; g.rays = rays;
     camera_rays_kernel<<<dim3((uint32_t)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream>>>(g);
     return check_launch("camera_rays");
-}
-
-extern "C" int gsx_camera_rays(const float *viewmats, const float *viewmats_rs, const float *Ks, const float *radial,
-                               const float *tangential, const float *thin_prism, const float *fisheye_max_angle,
-                               const float *ftheta, uint32_t n_images, uint32_t width, uint32_t height, int camera_model,
-                               int rs_type, float *rays, void *stream)
-{
-    return camera_rays_impl(viewmats, viewmats_rs, Ks, radial, tangential, thin_prism, fisheye_max_angle, ftheta, nullptr, n_images,
-                            width, height, camera_model, rs_type, rays, stream);
-}
-// ... behind a windshield: `ext` = HOST array of 84 floats (horizontal | vertical | horizontal inverse | vertical inverse
-// polynomial, order-5 layout of 21 coefficients each: BivariateWindshieldModelParameters, ExternalDistortion.h); the camera
-// model's ray is taken through the INVERSE polynomials (BaseCameraModel::image_point_to_camera_ray, Cameras.cuh:473-484)
-extern "C" int gsx_camera_rays_ext(const float *viewmats, const float *viewmats_rs, const float *Ks, const float *radial,
-                                   const float *tangential, const float *thin_prism, const float *fisheye_max_angle,
-                                   const float *ftheta, const float *ext, uint32_t n_images, uint32_t width, uint32_t height,
-                                   int camera_model, int rs_type, float *rays, void *stream)
-{
-    return camera_rays_impl(viewmats, viewmats_rs, Ks, radial, tangential, thin_prism, fisheye_max_angle, ftheta, ext, n_images,
-                            width, height, camera_model, rs_type, rays, stream);
-}
-// gsx_project_ut_rs_fwd behind a windshield (`ext` as above): every sigma point's ray is taken through the FORWARD polynomials
-// before the camera model projects it (BaseCameraModel::camera_ray_to_image_point, Cameras.cuh:462-470)
-extern "C" int gsx_project_ut_ext_fwd(const float *means, const float *quats, const float *scales, const float *opacities,
-                                      const float *viewmats0, const float *viewmats1, const float *Ks, const float *radial,
-                                      const float *tangential, const float *thin_prism, const float *fisheye_max_angle,
-                                      const float *ftheta, const float *ext, uint32_t B, uint32_t C, uint32_t N, uint32_t width,
-                                      uint32_t height, float eps2d, float near_plane, float far_plane, float radius_clip,
-                                      int camera_model, int rs_type, int global_z_order, float ut_alpha, float ut_beta,
-                                      float ut_kappa, float in_image_margin_factor, int require_all_sigma_points_valid,
-                                      int32_t *radii, float *means2d, float *depths, float *conics, float *compensations,
-                                      void *stream)
-{
-    return project_ut_launch(means, quats, scales, opacities, viewmats0, Ks, radial, tangential, thin_prism, fisheye_max_angle, ftheta,
-                             B, C, N, width, height, eps2d, near_plane, far_plane, radius_clip, camera_model, ut_alpha, ut_beta,
-                             ut_kappa, in_image_margin_factor, require_all_sigma_points_valid, radii, means2d, depths, conics,
-                             compensations, stream, viewmats1, rs_type, global_z_order, ext);
 }
 
 // gsplat::distort_camera_rays / gsplat::eval_bivariate_poly (ExternalDistortionWrappers.cu:30-160): the windshield model on a
@@ -927,10 +866,10 @@ extern "C" int gsx_project_ut_lidar_fwd(const float *means, const float *quats, 
 {
     LidarHost l{fov_horiz_start, fov_horiz_span, fov_vert_start, fov_vert_span, spinning_ccw, angles_to_columns_map,
                 (int)map_h, (int)map_w, (int)n_columns};
-    return project_ut_launch(means, quats, scales, opacities, viewmats0, Ks, nullptr, nullptr, nullptr, nullptr, nullptr, B, C, N,
-                             n_columns, map_h, eps2d, near_plane, far_plane, radius_clip, 4, ut_alpha, ut_beta, ut_kappa,
-                             in_image_margin_factor, require_all_sigma_points_valid, radii, means2d, depths, conics, compensations,
-                             stream, viewmats1, rs_type, global_z_order, nullptr, &l);
+    return project_ut_launch("gsx_project_ut_lidar_fwd", means, quats, scales, opacities, viewmats0, viewmats1, Ks, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, &l, B, C, N, n_columns, map_h, eps2d, near_plane, far_plane,
+                             radius_clip, 4, rs_type, global_z_order, ut_alpha, ut_beta, ut_kappa, in_image_margin_factor,
+                             require_all_sigma_points_valid, radii, means2d, depths, conics, compensations, stream);
 }
 
 // World rays of a spinning lidar's elements, [I, n_rows, n_columns, 6] (origin | unit direction; the zero ray for an element

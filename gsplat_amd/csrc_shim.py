@@ -10,15 +10,11 @@ from __future__ import annotations
 
 import enum
 
-from . import _ops  # noqa: F401  (TORCH_LIBRARY(gsplat) equivalent: schemas + CUDA-key impls)
+from . import _ops  # (TORCH_LIBRARY(gsplat) equivalent: schemas + CUDA-key impls)
 
 
-class CameraModelType(enum.IntEnum):  # gsplat/cuda/include/Common.h:75-82
-    PINHOLE = 0
-    ORTHO = 1
-    FISHEYE = 2
-    FTHETA = 3
-    LIDAR = 4
+# gsplat/cuda/include/Common.h:75-82: PINHOLE = 0 .. LIDAR = 4, from the one table
+CameraModelType = enum.IntEnum("CameraModelType", {name.upper(): i for name, i in _ops.CAMERA_MODEL_IDS.items()})
 
 
 class RendererConfig(enum.IntEnum):  # ext.cpp:66-77

@@ -1,4 +1,4 @@
-"""gsplat.rasterization() for the classic 3DGS path, orchestrated over the gfx950 stage ops.
+"""gsplat.rasterization() for the classic 3DGS path and the 3DGUT path, orchestrated over the gfx950 stage ops.
 
 Mirrors the public signature, argument meaning, output shapes, ``meta`` dict and error behaviour
 of the reference (``gsplat/rendering.py:234-690``) and the stage order of its C++ orchestrator
@@ -26,6 +26,7 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch import Tensor
 
+from ._ops import ROLLING_SHUTTER_GLOBAL
 from ._wrapper import (
     fully_fused_projection,
     isect_offset_encode,
@@ -104,7 +105,7 @@ def rasterization(
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Rasterize a set of 3D Gaussians (N) to a batch of image planes (C). See the reference
     docstring (``gsplat/rendering.py:292-525``) for the meaning of every argument; this
-    implementation covers the classic (EWA, non-3DGUT) path."""
+    implementation covers the classic (EWA) path and the 3DGUT path (``with_ut`` / ``with_eval3d``, see the module docstring)."""
     if render_mode not in _COLOR_MODES + ("D", "ED") + _HIT_MODES:
         raise ValueError(f"Unsupported render_mode: {render_mode}")
     if rasterize_mode not in ("classic", "antialiased"):
@@ -188,7 +189,7 @@ def rasterization(
         clear_row_map_cache()  # the previous step's row map (and the id tensors it holds) can go
     calc_comp = rasterize_mode == "antialiased"
     view_opacities = None
-    rs_type = _ROLLING_SHUTTER_GLOBAL if rolling_shutter is None else int(rolling_shutter)
+    rs_type = ROLLING_SHUTTER_GLOBAL if rolling_shutter is None else int(rolling_shutter)
     # rolling shutter (with_ut only, validated above): the projection interpolates the pose per sigma point, the from-world
     # rasterizer per pixel row / column, and the view-dependent colours use the camera offset averaged over the two ends of
     # the frame (Rendering.cpp:1057, SphericalHarmonics.cuh:40-65) - a synthetic view matrix built with differentiable tensor
@@ -406,9 +407,6 @@ def _check(cond: bool, *msg) -> None:
         raise RuntimeError("".join(str(m) for m in msg))
 
 
-_ROLLING_SHUTTER_GLOBAL = 4  # gsplat/cuda/_wrapper.py RollingShutterType.GLOBAL
-
-
 def _validate_rasterization_inputs(means, covars, quats, scales, opacities, colors, viewmats, Ks, *, render_mode,
                                    rasterize_mode, sh_degree, packed, sparse_grad, absgrad, distributed, camera_model,
                                    with_ut, with_eval3d, return_normals, global_z_order, rays, radial_coeffs,
@@ -421,7 +419,7 @@ def _validate_rasterization_inputs(means, covars, quats, scales, opacities, colo
     classic kernels are compiled for 4 and 16 only), and the checks run before any kernel or collective."""
     has_color = render_mode.startswith("RGB")
     hit = render_mode in _HIT_MODES
-    rs_global = rolling_shutter is None or int(rolling_shutter) == _ROLLING_SHUTTER_GLOBAL
+    rs_global = rolling_shutter is None or int(rolling_shutter) == ROLLING_SHUTTER_GLOBAL
     if distributed:  # named first, so that the error is about the distributed limitation (Rendering.cpp:187-233)
         _check(means.dim() == 2, "distributed=True does not support batch dimensions")
         _check(not sparse_grad, "distributed=True does not support sparse_grad=True")

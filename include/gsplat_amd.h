@@ -240,53 +240,46 @@ int gsx_sh_bwd(int degrees_to_use, const float *means, const float *viewmats, co
 /* ---------------------------------------------------------------------------------------------
  * Unscented-Transform projection (3DGUT): gsplat::projection_ut_3dgs_fused (ext.cpp:1230-1239; kernel
  * ProjectionUT3DGSFused.cu; algorithm as gsplat/cuda/_torch_impl_ut.py:69-644). Forward only - the op carries no gradient.
- * Dense rows [B,C,N]. camera_model 0 = pinhole (optionally OpenCV-distorted: radial [B,C,6] (k1..k6; pad 4 -> 6 with
- * zeros), tangential [B,C,2], thin_prism [B,C,4]; NULL = absent), 1 = orthographic (no coefficients), 2 = OpenCV fisheye
- * (k1..k4 in radial[..., 0:4]; fisheye_max_angle [B,C] = largest ray angle the model projects, i.e. where
- * d/dtheta of theta (1 + k1 theta^2 + .. + k4 theta^8) first vanishes, capped at the image corner - computed by the
- * caller, _torch_cameras.py:1344-1521). Global shutter.
- * Seven sigma points mean, mean +- sqrt(3 + lambda) scale_i R[:, i] (lambda = alpha^2 (3 + kappa) - 3) go through the
+ * Dense rows [B,C,N]. One entry for camera_model 0 .. 3 (a spinning lidar, 4, has a record of its own:
+ * gsx_project_ut_lidar_fwd below), global or rolling shutter, z or Euclidean sort depth, with or without a windshield.
+ * Seven sigma points mean, mean +- sqrt(3 + lambda) scale_i R[:, i] (lambda = alpha^2 (3 + kappa) - 3 > -3) go through the
  * camera model; mean2d / cov2d are the UT-weighted moments of their pixels (sums stop at the first invalid point when
- * require_all_sigma_points_valid). Then blur (+eps2d I) and compensation, conic = inverse, opacity-aware extent (opacities
- * NULL = none), eigenvalue-bounded radii, radius clip, image cull. Rows that fail a check are written as zeros.
- * compensations may be NULL. f-theta cameras: gsx_project_ut_ftheta_fwd below; rolling shutter: gsx_project_ut_rs_fwd. Lidar is not built: -1.
+ * require_all_sigma_points_valid). Then blur (+eps2d I) and compensation, conic = inverse, opacity-aware extent, eigenvalue-
+ * bounded radii, radius clip, image cull. Rows that fail a check are written as zeros. B * C * N = 0 returns GSX_OK untouched.
+ * Pointers that may be NULL, and what NULL means:
+ *   opacities          no opacity-aware extent
+ *   radial [B,C,6], tangential [B,C,2], thin_prism [B,C,4]   that distortion term is absent. camera_model 0 = pinhole takes any
+ *                      of them (OpenCV: k1..k6; pad 4 -> 6 with zeros); 1 = orthographic and 3 = f-theta take none; 2 = OpenCV
+ *                      fisheye takes radial only (k1..k4 in radial[..., 0:4])
+ *   fisheye_max_angle [B,C]   required for camera_model 2, not read otherwise: the largest ray angle the model projects, i.e.
+ *                      where d/dtheta of theta (1 + k1 theta^2 + .. + k4 theta^8) first vanishes, capped at the image corner -
+ *                      computed by the caller (_torch_cameras.py:1344-1521)
+ *   ftheta             required for camera_model 3, not read otherwise: a HOST array of 17 floats, one record per call (as in the
+ *                      reference) - reference_poly (0 / 1), pixeldist_to_angle_poly[6], angle_to_pixeldist_poly[6] (lowest degree
+ *                      first), max_angle, linear_cde[3] (FThetaCameraDistortionParameters, Cameras.h:103-117 / ext.cpp:165-226).
+ *                      The pixel distance from the principal point is a polynomial of the ray angle - `angle_to_pixeldist_poly`
+ *                      when reference_poly = 1, three Newton steps on `pixeldist_to_angle_poly` from that start when 0 - the
+ *                      angle is clamped at max_angle (rays beyond it are invalid; there is no in-front test), pixel = (c, d; e, 1)
+ *                      offset + principal point + 0.5
+ *   ext                no windshield. Else the 84-float HOST record described at gsx_camera_rays: every sigma point's ray goes
+ *                      through the FORWARD polynomials before the camera model (Cameras.cuh:462-470; orthographic :795-829)
+ *   viewmats1 [B,C,4,4]   required unless rs_type = 4 (then not read): the pose at the END of the frame
+ *   compensations      not wanted
+ * `rs_type` 0 top-to-bottom, 1 left-to-right, 2 bottom-to-top, 3 right-to-left, 4 global (Cameras.h:38-45;
+ * ProjectionUT3DGSFused.cu:121-127, 239-240, 411; Cameras.cuh:76-135, 362-429, 549-660). Under a rolling shutter every sigma
+ * point is projected with the start pose (else the end pose), then up to ten rounds of "read-out time of its pixel -> pose at
+ * that time (translation lerp, rotation slerp) -> project again"; the Gaussian's own camera-frame position (near / far, depth)
+ * uses the pose at mid-frame. `global_z_order` 1: depths = mean_c.z; 0: depths = |mean_c|, and f-theta cameras cull near / far
+ * on |mean_c|.
  * ------------------------------------------------------------------------------------------- */
 int gsx_project_ut_fwd(const float *means, const float *quats, const float *scales, const float *opacities,
-                       const float *viewmats, const float *Ks, const float *radial, const float *tangential,
-                       const float *thin_prism, const float *fisheye_max_angle, uint32_t B, uint32_t C, uint32_t N,
-                       uint32_t width, uint32_t height,
-                       float eps2d, float near_plane, float far_plane, float radius_clip, int camera_model,
-                       float ut_alpha, float ut_beta, float ut_kappa, float in_image_margin_factor,
-                       int require_all_sigma_points_valid, int32_t *radii, float *means2d, float *depths,
-                       float *conics, float *compensations, void *stream);
-/* The same op for camera_model 3, f-theta (gsplat/cuda/_torch_cameras.py FThetaCamera; parameter record
- * FThetaCameraDistortionParameters, Cameras.h:103-117 / ext.cpp:165-226): the pixel distance from the principal point is a
- * polynomial of the ray angle - `angle_to_pixeldist_poly` when reference_poly = 1, three Newton steps on
- * `pixeldist_to_angle_poly` from that start when reference_poly = 0 - the angle is clamped at max_angle (rays beyond it are
- * invalid; there is no in-front test), pixel = (c, d; e, 1) offset + principal point + 0.5. `ftheta` is a HOST array of 17
- * floats: reference_poly (0 / 1), pixeldist_to_angle_poly[6], angle_to_pixeldist_poly[6] (lowest degree first), max_angle,
- * linear_cde[3]. One record per call (as in the reference); everything else as gsx_project_ut_fwd. */
-int gsx_project_ut_ftheta_fwd(const float *means, const float *quats, const float *scales, const float *opacities,
-                              const float *viewmats, const float *Ks, const float *ftheta, uint32_t B, uint32_t C, uint32_t N,
-                              uint32_t width, uint32_t height, float eps2d, float near_plane, float far_plane, float radius_clip,
-                              float ut_alpha, float ut_beta, float ut_kappa, float in_image_margin_factor,
-                              int require_all_sigma_points_valid, int32_t *radii, float *means2d, float *depths,
-                              float *conics, float *compensations, void *stream);
-/* The same op with a ROLLING SHUTTER and / or the Euclidean sort depth, for every camera model above (ProjectionUT3DGSFused.cu:
- * 121-127, 239-240, 411; Cameras.cuh:76-135, 362-429, 549-660): `viewmats1` [B,C,4,4] = pose at the END of the frame (NULL with
- * rs_type 4), `rs_type` 0 top-to-bottom, 1 left-to-right, 2 bottom-to-top, 3 right-to-left, 4 global (Cameras.h:38-45). Every
- * sigma point is projected with the start pose (else the end pose), then up to ten rounds of "read-out time of its pixel -> pose at
- * that time (translation lerp, rotation slerp) -> project again"; the Gaussian's own camera-frame position (near / far, depth)
- * uses the pose at mid-frame. `global_z_order` 0: depths = |mean_c| instead of mean_c.z, and f-theta cameras cull near / far on
- * |mean_c|. `ftheta`: the 17-float HOST record of gsx_project_ut_ftheta_fwd (camera_model 3) or NULL. */
-int gsx_project_ut_rs_fwd(const float *means, const float *quats, const float *scales, const float *opacities,
-                          const float *viewmats0, const float *viewmats1, const float *Ks, const float *radial,
-                          const float *tangential, const float *thin_prism, const float *fisheye_max_angle,
-                          const float *ftheta, uint32_t B, uint32_t C, uint32_t N, uint32_t width, uint32_t height,
-                          float eps2d, float near_plane, float far_plane, float radius_clip, int camera_model,
-                          int rs_type, int global_z_order, float ut_alpha, float ut_beta, float ut_kappa,
-                          float in_image_margin_factor, int require_all_sigma_points_valid, int32_t *radii,
-                          float *means2d, float *depths, float *conics, float *compensations, void *stream);
+                       const float *viewmats0, const float *viewmats1, const float *Ks, const float *radial,
+                       const float *tangential, const float *thin_prism, const float *fisheye_max_angle, const float *ftheta,
+                       const float *ext, uint32_t B, uint32_t C, uint32_t N, uint32_t width, uint32_t height, float eps2d,
+                       float near_plane, float far_plane, float radius_clip, int camera_model, int rs_type,
+                       int global_z_order, float ut_alpha, float ut_beta, float ut_kappa, float in_image_margin_factor,
+                       int require_all_sigma_points_valid, int32_t *radii, float *means2d, float *depths, float *conics,
+                       float *compensations, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * From-world ("eval3d") compositing of 3DGUT, FORWARD: the compositing half of gsplat::rasterize_to_pixels_from_world_3dgs
@@ -297,34 +290,22 @@ int gsx_project_ut_rs_fwd(const float *means, const float *quats, const float *s
  * means [B,N,3], quats [B,N,4], scales [B,N,3]; colors [I,N,D], opacities [I,N] with I = B * cameras_per_batch and list rows
  * = image * N + gaussian (flatten_ids, isect_offsets as for gsx_raster3d_fwd); rays [I,H,W,6] = world-space origin | unit
  * direction per pixel (the caller generates them from its camera model). Outputs as gsx_raster3d_fwd, except
- * last_ids = -1 where no sample contributed. The backward pass is not built yet.
+ * last_ids = -1 where no sample contributed.
+ * `use_hit_distance`: the LAST colour channel of every sample is the distance along the ray to its closest approach in world
+ * units, |scale * (d' hit_t)|, instead of colors[row][cdim - 1] (RasterizeToPixelsFromWorld3DGS.cuh:715-720, 745-751).
+ * Pointers that may be NULL: backgrounds, masks (absent); sample_counts int32 [I,H,W] (not wanted; else the number of samples
+ * each pixel blended - the op's `return_sample_counts`, Rasterization.cpp:2404, `n_accumulated` in
+ * RasterizeToPixelsFromWorld3DGS.cuh:785); render_normals float [I,H,W,3] (not wanted; else sum of vis * the Gaussian's third
+ * axis R[:, 2], unit length, turned to face the ray, :762-768 - the op's `return_normals`, Rasterization.cpp:2656-2702); means,
+ * quats, scales, colors, opacities, flatten_ids when n_isects = 0.
  * ------------------------------------------------------------------------------------------- */
 int gsx_raster_world_fwd(const float *means, const float *quats, const float *scales, const float *colors,
                          const float *opacities, const float *rays, const float *backgrounds, const uint8_t *masks,
                          const int32_t *isect_offsets, const int32_t *flatten_ids, uint32_t n_images,
                          uint32_t cameras_per_batch, uint32_t n_gaussians, uint32_t n_isects, uint32_t cdim, uint32_t width,
-                         uint32_t height, uint32_t tile_size, uint32_t tile_w, uint32_t tile_h, float *render_colors,
-                         float *render_alphas, int32_t *last_ids, void *stream);
-/* The same launch + sample_counts int32 [I,H,W] (may be NULL): the number of samples each pixel blended - the op's
- * `return_sample_counts` output (Rasterization.cpp:2404; `n_accumulated` in RasterizeToPixelsFromWorld3DGS.cuh:785). */
-int gsx_raster_world_fwd_counts(const float *means, const float *quats, const float *scales, const float *colors,
-                                const float *opacities, const float *rays, const float *backgrounds, const uint8_t *masks,
-                                const int32_t *isect_offsets, const int32_t *flatten_ids, uint32_t n_images,
-                                uint32_t cameras_per_batch, uint32_t n_gaussians, uint32_t n_isects, uint32_t cdim,
-                                uint32_t width, uint32_t height, uint32_t tile_size, uint32_t tile_w, uint32_t tile_h,
-                                float *render_colors, float *render_alphas, int32_t *last_ids, int32_t *sample_counts,
-                                void *stream);
-/* ... + `use_hit_distance` (the LAST colour channel of every sample is the distance along the ray to its closest approach in
- * world units, |scale * (d' hit_t)|, instead of colors[row][cdim - 1]: RasterizeToPixelsFromWorld3DGS.cuh:715-720, 745-751) and
- * render_normals float [I,H,W,3] (may be NULL): sum of vis * the Gaussian's third axis R[:, 2], unit length, turned to face the
- * ray (:762-768) - the op's `use_hit_distance` / `return_normals` (Rasterization.cpp:2404, 2656-2702). */
-int gsx_raster_world_fwd_ex(const float *means, const float *quats, const float *scales, const float *colors,
-                            const float *opacities, const float *rays, const float *backgrounds, const uint8_t *masks,
-                            const int32_t *isect_offsets, const int32_t *flatten_ids, uint32_t n_images,
-                            uint32_t cameras_per_batch, uint32_t n_gaussians, uint32_t n_isects, uint32_t cdim,
-                            uint32_t width, uint32_t height, uint32_t tile_size, uint32_t tile_w, uint32_t tile_h,
-                            int use_hit_distance, float *render_colors, float *render_alphas, int32_t *last_ids,
-                            int32_t *sample_counts, float *render_normals, void *stream);
+                         uint32_t height, uint32_t tile_size, uint32_t tile_w, uint32_t tile_h, int use_hit_distance,
+                         float *render_colors, float *render_alphas, int32_t *last_ids, int32_t *sample_counts,
+                         float *render_normals, void *stream);
 
 /* Backward of gsx_raster_world_fwd (reference host fn rasterize_to_pixels_from_world_3dgs_bwd, Rasterization.cpp:2920;
  * kernel RasterizeToPixelsFromWorld3DGSParallelBatchBwd.cu:300-930). Gradient rows v_rows [I * N][row_stride >= 10 + cdim],
@@ -332,59 +313,39 @@ int gsx_raster_world_fwd_ex(const float *means, const float *quats, const float 
  * rotation vector w applied to the Gaussian's rotation (R -> exp([w]x) R); the caller sums the rows of one batch's cameras and
  * maps it to the raw quaternion: v_quat = (2 / |q|) (0, torque) (x) q / |q| (Hamilton product, w first). The reference forms
  * v_quats per sample from v_M (:840-890); the torque is the same derivative without the nine-term intermediate whose
- * stretch part cancels. render_alphas / last_ids are the forward outputs; v_render_alphas may be NULL. */
+ * stretch part cancels. render_alphas / last_ids are the forward outputs. n_isects = 0 returns GSX_OK with nothing read.
+ * With use_hit_distance (as in the forward) the hit distance's direct dependence on the scale goes into the v_scale columns and
+ * the last colour channel receives no colour gradient (:806-880).
+ * Pointers that may be NULL: backgrounds, masks (absent); v_render_alphas (zero cotangent); v_render_normals float [I,H,W,3]
+ * (normals were not rendered or carry no cotangent; else their share n0 x v_n0, n0 = the Gaussian's unit third axis, goes into
+ * the torque columns); v_rays float [I,H,W,6] (not wanted; else ZEROED by the caller: the cotangent of the rays, origin |
+ * direction - the reference's v_rays output, Rasterization.cpp:2920-3100; its tests differentiate with respect to the rays). */
 int gsx_raster_world_bwd(const float *means, const float *quats, const float *scales, const float *colors,
                          const float *opacities, const float *rays, const float *backgrounds, const uint8_t *masks,
                          const int32_t *isect_offsets, const int32_t *flatten_ids, const float *render_alphas,
                          const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
-                         uint32_t n_images, uint32_t cameras_per_batch, uint32_t n_gaussians, uint32_t n_isects,
-                         uint32_t cdim, uint32_t width, uint32_t height, uint32_t tile_size, uint32_t tile_w,
-                         uint32_t tile_h, float *v_rows, uint32_t row_stride, void *stream);
-/* Backward of gsx_raster_world_fwd_ex (RasterizeToPixelsFromWorld3DGSParallelBatchBwd.cu:806-880): the rows of
- * gsx_raster_world_bwd - the hit distance's direct dependence on the scale goes into the v_scale columns, the normals' share
- * (n0 x v_n0, n0 = the Gaussian's unit third axis) into the torque columns. With use_hit_distance the last colour channel
- * receives no colour gradient. v_render_normals float [I,H,W,3] may be NULL.
- * v_rays float [I,H,W,6] (may be NULL; zero-initialised by the caller): the cotangent of the rays, origin | direction - the
- * reference's v_rays output (Rasterization.cpp:2920-3100; its tests differentiate with respect to the rays). */
-int gsx_raster_world_bwd_ex(const float *means, const float *quats, const float *scales, const float *colors,
-                            const float *opacities, const float *rays, const float *backgrounds, const uint8_t *masks,
-                            const int32_t *isect_offsets, const int32_t *flatten_ids, const float *render_alphas,
-                            const int32_t *last_ids, const float *v_render_colors, const float *v_render_alphas,
-                            const float *v_render_normals, uint32_t n_images, uint32_t cameras_per_batch,
-                            uint32_t n_gaussians, uint32_t n_isects, uint32_t cdim, uint32_t width, uint32_t height,
-                            uint32_t tile_size, uint32_t tile_w, uint32_t tile_h, int use_hit_distance, float *v_rows,
-                            uint32_t row_stride, float *v_rays, void *stream);
+                         const float *v_render_normals, uint32_t n_images, uint32_t cameras_per_batch, uint32_t n_gaussians,
+                         uint32_t n_isects, uint32_t cdim, uint32_t width, uint32_t height, uint32_t tile_size,
+                         uint32_t tile_w, uint32_t tile_h, int use_hit_distance, float *v_rows, uint32_t row_stride,
+                         float *v_rays, void *stream);
 
 /* Rays of every pixel of I images, [I,H,W,6] = world-space origin | unit direction, the zero ray where the camera model cannot
  * invert the pixel (the from-world rasterizer gives such a pixel no samples): what the reference's kernels derive per thread when
  * no `rays` tensor is passed (compute_world_ray, RasterizeToPixelsFromWorld3DGS.cuh:349-529; element_to_world_ray_shutter_pose,
  * Cameras.cuh:503-546; the models' image_point_to_camera_ray: Cameras.cuh:717, 866, 1062-1290, 1472-1520, 1672-1760).
- * viewmats_rs NULL / rs_type 4 = global shutter. Coefficients as in gsx_project_ut_rs_fwd, one record per image: radial [I,6],
- * tangential [I,2], thin_prism [I,4], fisheye_max_angle [I]; `ftheta` = the 17-float HOST record of gsx_project_ut_ftheta_fwd. */
+ * camera_model 0 .. 3, rs_type and the coefficients with their NULL rules as in gsx_project_ut_fwd, one record per image: radial
+ * [I,6], tangential [I,2], thin_prism [I,4], fisheye_max_angle [I]; `ftheta` = its 17-float HOST record. viewmats_rs is required
+ * unless rs_type = 4 (then not read). I * width * height = 0 returns GSX_OK untouched.
+ * `ext` NULL = no windshield; else the external distortion, the reference's BivariateWindshieldModel (ExternalDistortion.h /
+ * .cuh; Python statement gsplat/cuda/_torch_external_distortion.py): a HOST array of 84 floats = horizontal | vertical |
+ * horizontal inverse | vertical inverse polynomial, each in the order-5 triangular layout of 21 coefficients (lower orders
+ * zero-padded the way pad_coefficients_to_max_order does, ExternalDistortion.cuh:104-124). Here the camera model's ray goes
+ * through the INVERSE polynomials (Cameras.cuh:473-484; orthographic :862-886). */
 int gsx_camera_rays(const float *viewmats, const float *viewmats_rs, const float *Ks, const float *radial,
                     const float *tangential, const float *thin_prism, const float *fisheye_max_angle, const float *ftheta,
-                    uint32_t n_images, uint32_t width, uint32_t height, int camera_model, int rs_type, float *rays,
-                    void *stream);
+                    const float *ext, uint32_t n_images, uint32_t width, uint32_t height, int camera_model, int rs_type,
+                    float *rays, void *stream);
 
-/* External (windshield) distortion, the reference's BivariateWindshieldModel (ExternalDistortion.h / .cuh; Python statement
- * gsplat/cuda/_torch_external_distortion.py). `ext` = HOST array of 84 floats: horizontal | vertical | horizontal inverse |
- * vertical inverse polynomial, each in the order-5 triangular layout of 21 coefficients (lower orders zero-padded the way
- * pad_coefficients_to_max_order does, ExternalDistortion.cuh:104-124).
- * gsx_camera_rays_ext = gsx_camera_rays behind the windshield (the camera model's ray goes through the inverse polynomials,
- * Cameras.cuh:473-484; orthographic :862-886); gsx_project_ut_ext_fwd = gsx_project_ut_rs_fwd behind it (every sigma point's
- * ray goes through the forward polynomials before the camera model, Cameras.cuh:462-470; orthographic :795-829). */
-int gsx_camera_rays_ext(const float *viewmats, const float *viewmats_rs, const float *Ks, const float *radial,
-                        const float *tangential, const float *thin_prism, const float *fisheye_max_angle, const float *ftheta,
-                        const float *ext, uint32_t n_images, uint32_t width, uint32_t height, int camera_model, int rs_type,
-                        float *rays, void *stream);
-int gsx_project_ut_ext_fwd(const float *means, const float *quats, const float *scales, const float *opacities,
-                           const float *viewmats0, const float *viewmats1, const float *Ks, const float *radial,
-                           const float *tangential, const float *thin_prism, const float *fisheye_max_angle, const float *ftheta,
-                           const float *ext, uint32_t B, uint32_t C, uint32_t N, uint32_t width, uint32_t height, float eps2d,
-                           float near_plane, float far_plane, float radius_clip, int camera_model, int rs_type,
-                           int global_z_order, float ut_alpha, float ut_beta, float ut_kappa, float in_image_margin_factor,
-                           int require_all_sigma_points_valid, int32_t *radii, float *means2d, float *depths, float *conics,
-                           float *compensations, void *stream);
 /* gsplat::distort_camera_rays / gsplat::eval_bivariate_poly (ExternalDistortionWrappers.cu:30-160): the model on n rays [n,3]
  * with ONE pair of polynomials (HOST arrays of 21 floats; the inverse pair undistorts), one bivariate polynomial at n points. */
 int gsx_distort_camera_rays(const float *rays, int64_t n, const float *horizontal_poly, const float *vertical_poly, float *out,

@@ -1,5 +1,5 @@
 """CPU oracle for the from-world ("eval3d") compositing of 3DGUT (TEST INFRASTRUCTURE ONLY; nothing under gsplat_amd/ may
-import it). The product kernels are csrc/raster_world.hip (gsx_raster_world_fwd / _fwd_ex / _bwd / _bwd_ex); this is the
+import it). The product kernels are csrc/raster_world.hip (gsx_raster_world_fwd / _bwd); this is the
 statement they are held to (tests/test_gpu_eval3d.py on the golden vectors, tests/test_gpu_world_fp64.py per element).
 
 Restates ``gsplat::rasterize_to_pixels_from_world_3dgs`` (reference kernels
@@ -82,7 +82,7 @@ def from_world(
     masks: Optional[Tensor] = None, use_hit_distance: bool = False, return_normals: bool = False, detail: bool = False,
     variant: Optional[str] = None,
 ):
-    """The whole statement of gsx_raster_world_fwd_ex, in the dtype of `means` (float32: M = S^-1 R^T assembled in float64 and
+    """The whole statement of gsx_raster_world_fwd, in the dtype of `means` (float32: M = S^-1 R^T assembled in float64 and
     rounded once, the kernel's contract; float64: nothing is rounded).
 
     means [G,N,3] / quats [G,N,4] / scales [G,N,3] (or without G): G groups of Gaussians shared by I / G consecutive images each

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Golden vectors for the external (windshield) distortion model (gsx_distort_camera_rays, gsx_eval_bivariate_poly and the
-`ext` record of gsx_camera_rays_ext / gsx_project_ut_ext_fwd) from the reference's Python statement of it
+`ext` record of gsx_camera_rays / gsx_project_ut_fwd) from the reference's Python statement of it
 (gsplat/cuda/_torch_external_distortion.py: `ref_eval_bivariate_poly`, `ref_distort_camera_ray` - the functions the reference's
 own tests/test_external_distortion.py compares its CUDA kernels with). Writes tests/golden/external_distortion_ref.npz
 (polynomials, inputs, the REFERENCE's outputs); tests/test_gpu_eval3d.py replays them on the GPU.

@@ -3,7 +3,7 @@
 (gsplat/cuda/_torch_impl_ut.py:306-644 `_fully_fused_projection_with_ut` with `rolling_shutter`, `viewmats_rs`,
 `global_z_order`; camera models and the rolling-shutter fixed point in gsplat/cuda/_torch_cameras.py:424-660, 2163-2210).
 Writes tests/golden/ut_rs_ref.npz = inputs + the REFERENCE's outputs; tests/test_gpu_ut.py replays them on the kernel
-(gsx_project_ut_rs_fwd). TEST INFRASTRUCTURE; run only where the reference checkout exists:
+(gsx_project_ut_fwd with rs_type 0 .. 3). TEST INFRASTRUCTURE; run only where the reference checkout exists:
     python oracle/pin_ut_rs_against_reference.py [--ref /root/reference]
 The parameter records (`torch.classes.gsplat.*`) come from this backend's libgsplat_amd_torch.so installed as `gsplat.csrc`;
 everything else in the reference module is plain torch on the CPU."""

@@ -1,6 +1,6 @@
 """Cases, float64 references, per-row error bounds and decided masks for the Unscented-Transform projection of
-csrc/projection_ut.hip (project_ut_kernel behind gsx_project_ut_fwd / _ftheta_fwd / _rs_fwd with a global shutter / _ext_fwd /
-_lidar_fwd). Shared by tests/test_ut_cases.py (CPU: the float32 restatement of oracle/ut.py lies inside every bound, the share of
+csrc/projection_ut.hip (project_ut_kernel behind gsx_project_ut_fwd - plain, f-theta, the Euclidean depth with a global shutter, the windshield - and
+gsx_project_ut_lidar_fwd). Shared by tests/test_ut_cases.py (CPU: the float32 restatement of oracle/ut.py lies inside every bound, the share of
 undecided rows is capped, wrong restatements fall outside) and tests/test_gpu_ut_fp64.py (GPU: the kernel against the same
 references and bounds). Everything here is seeded torch / numpy on the CPU; nothing imports the GPU package.
 

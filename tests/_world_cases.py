@@ -1,5 +1,5 @@
 """Cases, float64 reference, per-element error bounds and decided masks for the from-world (3DGUT) compositing pair of
-csrc/raster_world.hip (gsx_raster_world_fwd / _fwd_ex / _bwd / _bwd_ex behind rasterize_to_pixels_from_world_3dgs). Shared by
+csrc/raster_world.hip (gsx_raster_world_fwd / _bwd behind rasterize_to_pixels_from_world_3dgs). Shared by
 tests/test_world_cases.py (CPU: every case reaches its regime, the float32 statement lies inside every bound, wrong
 restatements fall outside) and tests/test_gpu_world_fp64.py (GPU: the kernels against the same reference and bounds).
 

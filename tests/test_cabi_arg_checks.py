@@ -1,4 +1,4 @@
-"""CPU: what the C-ABI entry points of the projection and compositing families answer to bad or empty arguments.
+"""CPU: what the C-ABI entry points of the projection, compositing and 3DGUT families answer to bad or empty arguments.
 
 Every case leaves its entry through a GSX_REQUIRE or through an early return that precedes the first HIP runtime call, so the
 test runs on a machine without a GPU. The library is called directly (gsplat_amd._cabi._lib): _cabi.call would ask torch for
@@ -384,6 +384,113 @@ R2D += [("gsx_raster2d_bwd_fill", dict(T16, v_rows_to_fill=-5, v_rows=P, row_str
         ("gsx_raster2d_bwd_fill", dict(T16, v_rows_to_fill=7, row_stride=20), OK, "")]
 
 
+# ---- 3DGUT: unscented projection and ray generation (projection_ut.hip), from-world compositing (raster_world.hip) -----------
+# A case that names `ftheta` or `ext` must fail a check: past the checks the entry reads those HOST records.
+UT_IN = _ptrs("means", "quats", "scales", "viewmats0", "Ks")
+UT_OUT = _ptrs("radii", "means2d", "depths", "conics")
+UT_OK = dict(ONE, **UT_IN, **UT_OUT, rs_type=4)  # passes everything up to the sigma-point weights (ut_alpha = 0)
+_rs = "rolling shutter type %d (0 .. 3 rolling, 4 global)"
+_models = "camera model %d is not built (pinhole = 0, orthographic = 1, fisheye = 2, f-theta = 3, lidar = 4 are)"
+_ortho = "the orthographic model takes no distortion coefficients"
+_fisheye = "the fisheye model needs fisheye_max_angle and takes radial coefficients only"
+_ftheta = "the f-theta model needs its parameter record and takes no other coefficients"
+
+UTP = []
+_e = "gsx_project_ut_fwd"
+UTP += [
+    (_e, dict(B=0, C=1, N=1, rs_type=4), OK, ""), (_e, dict(B=1, C=0, N=1, rs_type=4), OK, ""),
+    (_e, dict(B=1, C=1, N=0, rs_type=4), OK, ""),
+    (_e, dict(B=0, C=1, N=1, rs_type=5), ERR_ARG, f"{_e}: {_rs % 5}"),  # the shutter checks precede the empty return
+    (_e, dict(UT_OK, rs_type=5), ERR_ARG, f"{_e}: {_rs % 5}"),
+    (_e, dict(UT_OK, rs_type=-1), ERR_ARG, f"{_e}: {_rs % -1}"),
+    (_e, dict(UT_OK, rs_type=0), ERR_ARG, f"{_e}: a rolling shutter needs the end-of-frame poses"),
+    (_e, dict(ONE, rs_type=4), ERR_ARG, f"{_e}: null input"),
+    (_e, _drop(dict(UT_OK), "Ks"), ERR_ARG, f"{_e}: null input"),
+    (_e, dict(ONE, **UT_IN, rs_type=4), ERR_ARG, f"{_e}: null output"),
+    (_e, _drop(dict(UT_OK), "conics"), ERR_ARG, f"{_e}: null output"),
+    (_e, dict(UT_OK, camera_model=5), ERR_ARG, f"{_e}: {_models % 5}"),
+    (_e, dict(UT_OK, camera_model=-1), ERR_ARG, f"{_e}: {_models % -1}"),
+    (_e, dict(UT_OK, camera_model=4), ERR_ARG, f"{_e}: the lidar model (4) goes through gsx_project_ut_lidar_fwd"),
+    (_e, dict(UT_OK, camera_model=1, radial=P), ERR_ARG, f"{_e}: {_ortho}"),
+    (_e, dict(UT_OK, camera_model=1, thin_prism=P), ERR_ARG, f"{_e}: {_ortho}"),
+    (_e, dict(UT_OK, camera_model=2, radial=P), ERR_ARG, f"{_e}: {_fisheye}"),
+    (_e, dict(UT_OK, camera_model=2, fisheye_max_angle=P, tangential=P), ERR_ARG, f"{_e}: {_fisheye}"),
+    (_e, dict(UT_OK, camera_model=3), ERR_ARG, f"{_e}: {_ftheta}"),
+    (_e, dict(UT_OK, camera_model=3, ftheta=P, radial=P), ERR_ARG, f"{_e}: {_ftheta}"),
+    (_e, dict(UT_OK), ERR_ARG, f"{_e}: alpha^2 (3 + kappa) must be positive"),  # ut_alpha = 0: 3 + lambda = 0
+    (_e, dict(UT_OK, rs_type=2, viewmats1=P, ut_alpha=1.0, ut_kappa=-3.0), ERR_ARG, f"{_e}: alpha^2 (3 + kappa) must be positive"),
+]
+_e = "gsx_project_ut_lidar_fwd"  # the same body: its messages carry the lidar entry's name
+UTP += [
+    (_e, dict(B=1, C=1, N=0, rs_type=4), OK, ""),
+    (_e, dict(UT_OK, rs_type=5), ERR_ARG, f"{_e}: {_rs % 5}"),
+    (_e, dict(UT_OK, rs_type=1), ERR_ARG, f"{_e}: a rolling shutter needs the end-of-frame poses"),
+    (_e, dict(ONE, rs_type=4), ERR_ARG, f"{_e}: null input"),
+    (_e, dict(ONE, **UT_IN, rs_type=4), ERR_ARG, f"{_e}: null output"),
+    (_e, dict(UT_OK, rs_type=1, viewmats1=P), ERR_ARG, f"{_e}: a rolling shutter needs the angles_to_columns_map"),
+    (_e, dict(UT_OK, rs_type=1, viewmats1=P, angles_to_columns_map=P, map_h=2, map_w=2, n_columns=1), ERR_ARG,
+     f"{_e}: a rolling shutter needs the angles_to_columns_map"),
+    (_e, dict(UT_OK, rs_type=1, viewmats1=P, angles_to_columns_map=P, map_h=2, map_w=2, n_columns=2), ERR_ARG,
+     f"{_e}: alpha^2 (3 + kappa) must be positive"),
+    (_e, dict(UT_OK), ERR_ARG, f"{_e}: alpha^2 (3 + kappa) must be positive"),
+]
+
+RAYS = []
+_e = "gsx_camera_rays"
+RAY_OK = dict(n_images=1, width=5, height=3, rs_type=4, **_ptrs("viewmats", "Ks", "rays"))
+RAYS += [
+    (_e, dict(n_images=0, width=5, height=3), OK, ""), (_e, dict(n_images=1, width=0, height=3), OK, ""),
+    (_e, dict(n_images=1, width=5, height=0, rs_type=7, camera_model=9), OK, ""),  # no pixels: nothing is checked
+    (_e, dict(n_images=1, width=5, height=3, rs_type=4), ERR_ARG, f"{_e}: null pointer"),
+    (_e, _drop(dict(RAY_OK), "rays"), ERR_ARG, f"{_e}: null pointer"),
+    (_e, dict(RAY_OK, camera_model=4), ERR_ARG, f"{_e}: camera model 4 is not built (pinhole 0, ortho 1, fisheye 2, f-theta 3)"),
+    (_e, dict(RAY_OK, camera_model=-1), ERR_ARG, f"{_e}: camera model -1 is not built (pinhole 0, ortho 1, fisheye 2, f-theta 3)"),
+    (_e, dict(RAY_OK, rs_type=5), ERR_ARG, f"{_e}: {_rs % 5}"),
+    (_e, dict(RAY_OK, rs_type=-1), ERR_ARG, f"{_e}: {_rs % -1}"),
+    (_e, dict(RAY_OK, rs_type=3), ERR_ARG, f"{_e}: a rolling shutter needs the end-of-frame poses"),
+    (_e, dict(RAY_OK, camera_model=1, tangential=P), ERR_ARG, f"{_e}: {_ortho}"),
+    (_e, dict(RAY_OK, camera_model=2, radial=P), ERR_ARG, f"{_e}: {_fisheye}"),
+    (_e, dict(RAY_OK, camera_model=2, fisheye_max_angle=P, thin_prism=P), ERR_ARG, f"{_e}: {_fisheye}"),
+    (_e, dict(RAY_OK, camera_model=3), ERR_ARG, f"{_e}: {_ftheta}"),
+    (_e, dict(RAY_OK, camera_model=3, ftheta=P, tangential=P), ERR_ARG, f"{_e}: {_ftheta}"),
+]
+
+WORLD = []
+_e = "gsx_raster_world_fwd"
+W_CAM = dict(T16, cameras_per_batch=1)
+W_OUT = _ptrs("render_colors", "render_alphas", "last_ids", "isect_offsets", "rays")  # what the entry needs without any list
+W_IN = _ptrs("means", "quats", "scales", "colors", "opacities", "flatten_ids")
+_dims = "channels and cameras_per_batch must be >= 1"
+WORLD += [
+    (_e, dict(tile_size=0, cdim=3, cameras_per_batch=1), ERR_ARG, f"{_e}: tile_size must be in [1,16], got 0"),
+    (_e, dict(tile_size=17, cdim=3, cameras_per_batch=1), ERR_ARG, f"{_e}: tile_size must be in [1,16], got 17"),
+    (_e, dict(tile_size=16, cdim=0, cameras_per_batch=1), ERR_ARG, f"{_e}: {_dims}"),
+    (_e, dict(T16), ERR_ARG, f"{_e}: {_dims}"),  # cameras_per_batch = 0
+    (_e, dict(W_CAM), ERR_ARG, f"{_e}: null pointer"),
+    (_e, _drop(dict(W_CAM, **W_OUT), "last_ids"), ERR_ARG, f"{_e}: null pointer"),
+    (_e, _drop(dict(W_CAM, **W_OUT), "rays"), ERR_ARG, f"{_e}: null pointer"),
+    (_e, dict(W_CAM, **W_OUT, n_isects=1), ERR_ARG, f"{_e}: null input"),
+    (_e, _drop(dict(W_CAM, **W_OUT, **W_IN, n_isects=1), "quats"), ERR_ARG, f"{_e}: null input"),
+]
+_e = "gsx_raster_world_bwd"
+W_BWD_IN = dict(W_IN, **_ptrs("rays", "isect_offsets", "render_alphas", "last_ids", "v_render_colors"))
+_rows = "gradient rows missing or too narrow (10 + cdim columns)"
+WORLD += [
+    (_e, dict(tile_size=0, cdim=3, cameras_per_batch=1), ERR_ARG, f"{_e}: tile_size must be in [1,16], got 0"),
+    (_e, dict(tile_size=17, cdim=3, cameras_per_batch=1), ERR_ARG, f"{_e}: tile_size must be in [1,16], got 17"),
+    (_e, dict(tile_size=16, cdim=0, cameras_per_batch=1), ERR_ARG, f"{_e}: {_dims}"),
+    (_e, dict(T16), ERR_ARG, f"{_e}: {_dims}"),
+    (_e, dict(W_CAM), OK, ""),  # n_isects == 0 returns before the row checks
+    (_e, dict(W_CAM, use_hit_distance=1, v_render_normals=P, v_rays=P), OK, ""),
+    (_e, dict(W_CAM, n_isects=1), ERR_ARG, f"{_e}: {_rows}"),
+    (_e, dict(W_CAM, n_isects=1, v_rows=P, row_stride=12), ERR_ARG, f"{_e}: {_rows}"),  # 9 + cdim
+    (_e, dict(W_CAM, n_isects=1, v_rows=P, row_stride=13), ERR_ARG, f"{_e}: null input"),
+    (_e, _drop(dict(W_CAM, n_isects=1, v_rows=P, row_stride=13, **W_BWD_IN), "rays"), ERR_ARG, f"{_e}: null input"),
+    (_e, _drop(dict(W_CAM, n_isects=1, v_rows=P, row_stride=13, **W_BWD_IN, use_hit_distance=1, v_render_normals=P), "last_ids"),
+     ERR_ARG, f"{_e}: null input"),
+]
+
+
 def _ids(cases):
     return [f"{i}-{c[0][4:]}-{'ok' if c[2] == OK else c[3].split(': ', 1)[1][:28]}" for i, c in enumerate(cases)]
 
@@ -406,6 +513,24 @@ def test_3dgs_compositing_entries(entry, kw, rc, msg):
 @pytest.mark.parametrize("entry,kw,rc,msg", R2D, ids=_ids(R2D))
 def test_2dgs_compositing_entries(entry, kw, rc, msg):
     _check(entry, kw, rc, msg)
+
+
+@pytest.mark.parametrize("entry,kw,rc,msg", UTP, ids=_ids(UTP))
+def test_ut_projection_entries(entry, kw, rc, msg):
+    _check(entry, kw, rc, msg)
+    assert rc == OK or msg.startswith(entry + ": ")
+
+
+@pytest.mark.parametrize("entry,kw,rc,msg", RAYS, ids=_ids(RAYS))
+def test_camera_ray_entries(entry, kw, rc, msg):
+    _check(entry, kw, rc, msg)
+    assert rc == OK or msg.startswith(entry + ": ")
+
+
+@pytest.mark.parametrize("entry,kw,rc,msg", WORLD, ids=_ids(WORLD))
+def test_from_world_entries(entry, kw, rc, msg):
+    _check(entry, kw, rc, msg)
+    assert rc == OK or msg.startswith(entry + ": ")
 
 
 def test_a_successful_call_keeps_the_last_message():

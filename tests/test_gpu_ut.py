@@ -130,7 +130,7 @@ def _rs_cases():
                                   "rs_right_left_fisheye", "rs_top_bottom_ortho", "rs_left_right_ftheta", "rs_top_bottom_distance",
                                   "global_distance_pinhole", "global_distance_ftheta"])
 def test_ut_projection_rolling_shutter_and_distance_depth_match_reference_outputs(G, name):
-    """gsx_project_ut_rs_fwd against the outputs of the reference's own torch statement with a ROLLING shutter (every shutter
+    """gsx_project_ut_fwd against the outputs of the reference's own torch statement with a ROLLING shutter (every shutter
     direction, every camera model) and with global_z_order=False (tests/golden/ut_rs_ref.npz, written by
     oracle/pin_ut_rs_against_reference.py). The read-out time is floor(pixel row or column) / (size - 1): a sigma point that lands
     within rounding of a row boundary takes the neighbouring row's pose in one of the two evaluations and moves by the motion of

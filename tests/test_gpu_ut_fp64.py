@@ -1,4 +1,4 @@
-"""GPU: the Unscented-Transform projection (project_ut_kernel of csrc/projection_ut.hip, through its four C entry points and the
+"""GPU: the Unscented-Transform projection (project_ut_kernel of csrc/projection_ut.hip, through gsx_project_ut_fwd and the
 lidar entry) against the float64 references, per-row bounds and decided masks of tests/_ut_cases.py - every camera model and
 route, six cameras that all differ, a batch, the launch edges - and the ray generation of the same file (camera_rays_kernel)
 against the same float64 forward models: every generated ray, sent back through the forward model, lands on its pixel centre.

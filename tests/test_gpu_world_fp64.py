@@ -109,7 +109,7 @@ def _cabi_forward(cs, a):
     last_ids = torch.full((I, H, W), -7, device=DEV, dtype=torch.int32)
     counts = torch.full((I, H, W), -7, device=DEV, dtype=torch.int32)
     normals = torch.full((I, H, W, 3), float("nan"), device=DEV) if cs.normals else None
-    _cabi.call("gsx_raster_world_fwd_ex", a["means"], a["quats"], a["scales"], a["colors"], a["opacities"], a["rays"], a["bg"],
+    _cabi.call("gsx_raster_world_fwd", a["means"], a["quats"], a["scales"], a["colors"], a["opacities"], a["rays"], a["bg"],
                a["masks"], a["off"], a["fl"], I, cs.C, cs.N, a["fl"].numel(), D, W, H, cs.ts, cs.tw, cs.th, int(cs.hit), renders,
                alphas, last_ids, counts, normals)
     return renders, alphas, last_ids, counts, normals
@@ -117,13 +117,14 @@ def _cabi_forward(cs, a):
 
 @pytest.mark.parametrize("name", CABI_FWD_CASES)
 def test_forward_c_entry_within_fp64_bounds(G, name):
-    """gsx_raster_world_fwd_ex through _cabi.call, into outputs pre-filled with NaN / -7: every pixel is written."""
+    """gsx_raster_world_fwd through _cabi.call, into outputs pre-filled with NaN / -7: every pixel is written."""
     cs, ref = _reference(name)
     out = _cabi_forward(cs, _flat(cs))
     _check_forward(cs, ref, name, "forward (C entry)", *out)
 
 
-def _cabi_backward(cs, a, ref, alphas, last_ids, entry, want_rays):
+def _cabi_backward(cs, a, ref, alphas, last_ids, want_rays, plain=False):
+    """gsx_raster_world_bwd; `plain`: v_render_normals = NULL, use_hit_distance = 0 (and no v_rays), whatever the case has."""
     from gsplat_amd import _cabi
 
     I, D = cs.I, cs.D
@@ -131,44 +132,40 @@ def _cabi_backward(cs, a, ref, alphas, last_ids, entry, want_rays):
     v_r = cot.v_render.to(DEV)
     v_a = cot.v_alpha.to(DEV) if cot.v_alpha is not None else None
     rows = torch.zeros((I * cs.N, 10 + D), device=DEV)
-    head = (a["means"], a["quats"], a["scales"], a["colors"], a["opacities"], a["rays"], a["bg"], a["masks"], a["off"], a["fl"],
-            alphas, last_ids, v_r, v_a)
-    dims = (I, cs.C, cs.N, a["fl"].numel(), D, cs.W, cs.H, cs.ts, cs.tw, cs.th)
-    v_rays = None
-    if entry == "gsx_raster_world_bwd":
-        _cabi.call(entry, *head, *dims, rows, 10 + D)
-    else:
-        v_n = cot.v_normals.to(DEV) if cs.normals else None
-        v_rays = torch.zeros((I, cs.H, cs.W, 6), device=DEV) if want_rays else None
-        _cabi.call(entry, *head, v_n, *dims, int(cs.hit), rows, 10 + D, v_rays)
+    v_n = cot.v_normals.to(DEV) if cs.normals and not plain else None
+    v_rays = torch.zeros((I, cs.H, cs.W, 6), device=DEV) if want_rays else None
+    _cabi.call("gsx_raster_world_bwd", a["means"], a["quats"], a["scales"], a["colors"], a["opacities"], a["rays"], a["bg"],
+               a["masks"], a["off"], a["fl"], alphas, last_ids, v_r, v_a, v_n, I, cs.C, cs.N, a["fl"].numel(), D, cs.W, cs.H, cs.ts,
+               cs.tw, cs.th, 0 if plain else int(cs.hit), rows, 10 + D, v_rays)
     return rows.cpu(), (None if v_rays is None else v_rays.cpu())
 
 
 @pytest.mark.parametrize("name", wc.BACKWARD_CASES)
 def test_backward_rows_within_fp64_bounds(G, name):
-    """The C-ABI rows [I N][10 + D] of gsx_raster_world_bwd_ex (and of gsx_raster_world_bwd where no extra is requested) per
-    element, the rows that must stay exactly zero included (their bound is 0), with v_rays where the case asks for them; a second
-    run into fresh zeroed rows agrees within the unordered sums' term."""
+    """The C-ABI rows [I N][10 + D] of gsx_raster_world_bwd per element, the rows that must stay exactly zero included (their
+    bound is 0), with v_rays where the case asks for them; a second run into fresh zeroed rows agrees within the unordered sums'
+    term, and so does - where the case has neither hit distance nor normals - the call with NULL v_render_normals, use_hit_distance
+    0 and NULL v_rays."""
     cs, ref = _reference(name)
     a = _flat(cs)
     _, alphas, last_ids, _, _ = _cabi_forward(cs, a)
-    rows, v_rays = _cabi_backward(cs, a, ref, alphas, last_ids, "gsx_raster_world_bwd_ex", cs.want_rays)
+    rows, v_rays = _cabi_backward(cs, a, ref, alphas, last_ids, cs.want_rays)
     assert torch.isfinite(rows).all()
-    _report(name, "rows (_bwd_ex)", wc.compare_rows(cs, ref, rows, v_rays))
+    _report(name, "rows", wc.compare_rows(cs, ref, rows, v_rays))
     if cs.masks is not None:  # Gaussians seen only by masked tiles keep zero rows, masked pixels zero v_rays
         assert bool((ref.bwd_bounds.rows_mag.sum(1) == 0).any())
         assert v_rays is not None and bool((v_rays.reshape(-1, 6)[~ref.open_px] == 0).all())
     if ref.zero_ray.any() and v_rays is not None:
         assert bool((v_rays.reshape(-1, 6)[ref.zero_ray] == 0).all())
-    rows2, v_rays2 = _cabi_backward(cs, a, ref, alphas, last_ids, "gsx_raster_world_bwd_ex", cs.want_rays)
+    rows2, v_rays2 = _cabi_backward(cs, a, ref, alphas, last_ids, cs.want_rays)
     twice = 2.0 * ref.bwd_bounds.rows_sum
     assert wc.ratio(rows2 - rows, twice) <= 1.0, "a second run differs by more than the unordered sums allow"
     if v_rays is not None:
         assert torch.equal(v_rays, v_rays2)  # one lane owns a pixel: no unordered sum
     if not (cs.hit or cs.normals):
-        rows3, _ = _cabi_backward(cs, a, ref, alphas, last_ids, "gsx_raster_world_bwd", False)
-        _report(name, "rows (_bwd)", wc.compare_rows(cs, ref, rows3))
-        assert wc.ratio(rows3 - rows, twice) <= 1.0, "gsx_raster_world_bwd and _bwd_ex give different rows"
+        rows3, _ = _cabi_backward(cs, a, ref, alphas, last_ids, False, plain=True)
+        _report(name, "rows (no extras, no v_rays)", wc.compare_rows(cs, ref, rows3))
+        assert wc.ratio(rows3 - rows, twice) <= 1.0, "the rows differ between a call with and a call without v_rays"
 
 
 @pytest.mark.parametrize("name", wc.BACKWARD_CASES)

@@ -10,6 +10,7 @@ through their CUDA-key kernel up to the point where they would touch the device;
 tests/test_host_dry_run.py for the empty-scene path, whose control flow does not depend on kernel results.
 
     python tools/dry_run.py            # empty 3DGS / 2DGS scenes, dense and packed, forward + backward
+    python tools/dry_run.py cameras    # the 3DGUT projection and ray-generation op bodies for every camera model
 """
 import os
 import sys
@@ -105,8 +106,55 @@ def empty_scene(fn: str, packed: bool):
         assert out[0].shape == (C, H, W, 4) and out[6]["isect_ids"].numel() == 0
 
 
+def ut_cameras(calls):
+    """projection_ut_3dgs_fused and camera_pixel_rays for every camera model of the one entry each (pinhole, OpenCV pinhole,
+    ortho, fisheye, f-theta) under a global and a rolling shutter, behind a windshield, with the Euclidean sort depth: B = 1,
+    C = 2, N = 4, 5 x 3 pixels. call() checks every argument list against the header; the entries run their own checks and read
+    the host records. Returns the entry points these op bodies reached."""
+    from gsplat_amd import _ops
+
+    n0 = len(calls)
+    g = torch.Generator().manual_seed(3)
+    B, C, N, W, H = 1, 2, 4, 5, 3
+    means, quats = torch.randn(B, N, 3, generator=g), torch.randn(B, N, 4, generator=g)
+    scales, opacities = torch.rand(B, N, 3, generator=g) * 0.1, torch.rand(B, N, generator=g)
+    viewmats = torch.eye(4).expand(B, C, 4, 4).contiguous()
+    viewmats_rs = viewmats.clone()
+    viewmats_rs[..., 0, 3] = 0.1
+    Ks = torch.tensor([[4.0, 0.0, 2.5], [0.0, 4.0, 1.5], [0.0, 0.0, 1.0]]).expand(B, C, 3, 3).contiguous()
+    cls = torch.classes.gsplat
+    ftheta = cls.FThetaCameraDistortionParameters(
+        reference_poly=1, pixeldist_to_angle_poly=[0.0, 0.25, 0.0, 0.0, 0.0, 0.0], angle_to_pixeldist_poly=[0.0, 4.0, 0.0, 0.0, 0.0, 0.0],
+        max_angle=1.2, linear_cde=[1.0, 0.0, 0.0])
+    windshield = cls.BivariateWindshieldModelParameters()
+    windshield.horizontal_poly = windshield.horizontal_poly_inverse = torch.tensor([0.0, 1.0, 0.0])
+    windshield.vertical_poly = windshield.vertical_poly_inverse = torch.tensor([0.0, 0.0, 1.0])
+    radial6, radial4 = torch.full((B, C, 6), 0.01), torch.full((B, C, 4), 0.01)
+    tangential, thin_prism = torch.full((B, C, 2), 1e-3), torch.full((B, C, 4), 1e-3)
+    cameras = {  # name: (camera model id, radial, tangential, thin prism, f-theta record)
+        "pinhole": (0, None, None, None, None), "opencv": (0, radial6, tangential, thin_prism, None),
+        "opencv-radial4": (0, radial4, None, None, None), "ortho": (1, None, None, None, None),
+        "fisheye": (2, radial4, None, None, None), "fisheye-plain": (2, None, None, None, None),
+        "ftheta": (3, None, None, None, ftheta)}
+    runs = [(name, rs, True, None) for name in cameras for rs in (_ops.ROLLING_SHUTTER_GLOBAL, 1)]
+    runs += [("pinhole", _ops.ROLLING_SHUTTER_GLOBAL, True, windshield), ("ftheta", _ops.ROLLING_SHUTTER_GLOBAL, False, None)]
+    for name, rs, global_z, ext in runs:
+        model, radial, tang, prism, ft = cameras[name]
+        rolling = rs != _ops.ROLLING_SHUTTER_GLOBAL
+        out = _ops.projection_ut_3dgs_fused(means, quats, scales, opacities, viewmats, viewmats_rs if rolling else None, Ks, W, H,
+                                            0.3, 0.01, 1e10, 0.0, True, model, global_z, None, rs, radial, tang, prism, ft, None, ext)
+        assert out[0].shape == (B, C, N, 2) and out[0].dtype == torch.int32 and out[4].shape == (B, C, N)
+        rays = _ops.camera_pixel_rays(viewmats, viewmats_rs if rolling else None, Ks, W, H, model, rs, radial, tang, prism, ft, ext)
+        assert rays.shape == (B, C, H, W, 6)
+    assert len(calls) - n0 == 2 * len(runs)
+    return sorted(set(calls[n0:]))
+
+
 def main() -> int:
     calls = install()
+    if sys.argv[1:] == ["cameras"]:
+        print("cameras:", " ".join(ut_cameras(calls)))
+        return 0
     bad = 0
     for fn in ("3dgs", "2dgs"):
         for packed in (False, True):
