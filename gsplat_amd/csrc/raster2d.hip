@@ -116,14 +116,14 @@ __global__ void __launch_bounds__(256) raster2d_fwd_kernel(const Raster2DArgs a)
           bool hit         = false;
           if (tl < batch_size) {
               const float4 cu = s_cull[tl];
-              hit = (fabsf(cu.x - rect.cx) - rect.hw <= cu.z) && (fabsf(cu.y - rect.cy) - rect.hh <= cu.w);
+              hit = box_reaches_rect(cu.x, cu.y, cu.z, cu.w, rect);
               if (hit) hit = surfel_reaches_rect(s_A[tl], s_B[tl], s_C[tl], rect.cx - tcx, rect.cy - tcy, rect.hw, rect.hh);
           }
           uint64_t todo = __builtin_amdgcn_ballot_w64(hit);
           while (todo) {
             const int32_t bit = (int32_t)__builtin_ctzll(todo);
             const int32_t t   = j + bit;
-            asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit)); // todo &= todo - 1 in one scalar instruction
+            pop_lowest_bit(todo, bit);
             const Surfel s = eval_surfel(s_A[t], s_B[t], s_C[t], qx, qy, thr);
             // Branch-free body (raster3d_fwd.hip: the scalar unit, not the vector ALU, is the busy pipe when the pixel's
             // state lives in exec-style masks): `thr` is this pixel's alpha threshold, +inf once it is done.
@@ -328,14 +328,14 @@ __global__ void __launch_bounds__(256) raster2d_bwd_kernel(const Raster2DArgs a)
           bool hit         = false;
           if (tl >= t_first && tl < batch_size) {
               const float4 cu = s_cull[tl];
-              hit = (fabsf(cu.x - rect.cx) - rect.hw <= cu.z) && (fabsf(cu.y - rect.cy) - rect.hh <= cu.w);
+              hit = box_reaches_rect(cu.x, cu.y, cu.z, cu.w, rect);
               if (hit) hit = surfel_reaches_rect(s_Za[tl], s_Zb[tl], s_Zc[tl], rect.cx - tcx, rect.cy - tcy, rect.hw, rect.hh);
           }
           uint64_t todo = __builtin_amdgcn_ballot_w64(hit);
           while (todo) { // scalar loop over the survivors, back to front
             const int32_t bit = (int32_t)__builtin_ctzll(todo);
             const int32_t t   = j + bit;
-            asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit)); // todo &= todo - 1 in one scalar instruction
+            pop_lowest_bit(todo, bit);
             const float4 C = s_Zc[t];
             const Surfel s = eval_surfel(s_Za[t], s_Zb[t], C, qx, qy);
             const bool valid = inside && (batch_end - t <= bin_final) && s.valid;
@@ -703,7 +703,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSX_BWD
         uint64_t todo          = __builtin_amdgcn_ballot_w64(hitmask != 0);
         while (todo) {
             const int32_t t = (int32_t)__builtin_ctzll(todo);
-            asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(t));
+            pop_lowest_bit(todo, t);
             const int qm       = __builtin_amdgcn_readlane(hitmask, t);
             const float4 Za = s_Za[t], Zb = s_Zb[t], Zc = s_Zc[t];
             const float4 nr    = s_N[t];
@@ -808,7 +808,7 @@ static int launch2_fwd(const Raster2DArgs &a, hipStream_t stream)
 {
     const uint32_t n_blocks = a.tile_w * a.tile_h * a.n_images;
     if (n_blocks == 0) return GSX_OK;
-    const uint32_t grid  = ((n_blocks + 7u) / 8u) * 8u;
+    const uint32_t grid  = xcd_grid(n_blocks);
     const uint32_t block = a.tile_size <= 8 ? 64u : 256u;
     const size_t smem    = kBatch2 * (5 * sizeof(float4) + sizeof(float) * CH);
     raster2d_fwd_kernel<CH><<<dim3(grid), dim3(block), smem, stream>>>(a);
@@ -820,7 +820,7 @@ static int launch2_bwd(const Raster2DArgs &a, hipStream_t stream)
 {
     const uint32_t n_blocks = a.tile_w * a.tile_h * a.n_images;
     if (n_blocks == 0 || a.n_isects == 0) return GSX_OK;
-    const uint32_t grid  = ((n_blocks + 7u) / 8u) * 8u;
+    const uint32_t grid  = xcd_grid(n_blocks);
     const uint32_t block = a.tile_size <= 8 ? 64u : 256u;
     if constexpr (!ABS && CH <= 4) {
         // GSX_RASTER2D_BWD = h (default: one wave per half tile, 1.75 ms on c5) | r (the four-wave reduction kernel below, 1.83

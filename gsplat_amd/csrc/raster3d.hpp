@@ -136,6 +136,15 @@ inline auto with_channels(uint32_t n, F &&f)
     return f(std::integral_constant<int, 32>{});
 }
 
+// The grid of a per-tile launch: one workgroup per tile (dense) or per active tile (sparse), rounded up to the multiple of 8 that
+// xcd_remap() needs. 0 = nothing to launch.
+inline uint32_t xcd_grid(uint32_t n_blocks) { return ((n_blocks + 7u) / 8u) * 8u; }
+template <class Args> // Raster3DArgs, QueryArgs, the from-world arguments
+inline uint32_t tile_grid(const Args &a)
+{
+    return xcd_grid(a.sp_active_tiles ? a.n_active : a.tile_w * a.tile_h * a.n_images);
+}
+
 // Block index -> (image, tile) with an XCD-aware remap: hardware places workgroup b on
 // XCD b % 8 (MI355X_MICROARCH.md "Workgroup dispatch"); neighbouring tiles share Gaussians,
 // so give each XCD a contiguous run of tiles to keep those rows in ITS private L2.
@@ -147,9 +156,6 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t n_blocks)
     return (b % kXcds) * per_xcd + (b / kXcds);
 }
 
-// Which tile does this workgroup own, which slice of the sorted intersection list, and which output row does this lane
-// write? Dense: tile = block, row = pixel index in the [I, H, W] image. Sparse: tile = active_tiles[block], list slice from
-// the per-active-tile offsets, row = pixel_map[first row of the tile + rank of the lane's pixel among the set bits].
 // index of cotangent (pixel row `pix`, channel k) in v_render_colors: contiguous rows of cdim floats, or any layout that is
 // linear in the pixel index (an expanded scalar - the gradient of sum() - has both strides 0)
 template <typename Args>
@@ -162,7 +168,39 @@ struct TileCtx {
     uint32_t image_id, tile_id, tile_x, tile_y;
     int32_t range_start, range_end;
 };
-template <class Args> // Raster3DArgs or QueryArgs (raster_query.hip): same grid / layout field names
+// The pieces of the block -> tile mapping. Args = Raster3DArgs, QueryArgs (raster_query.hip): same grid / layout field names.
+// global tile id (image * tiles_per_image + tile) -> image, tile and the tile's position in the image
+template <class Args>
+__device__ __forceinline__ void tile_coords(const Args &a, uint32_t blk, TileCtx &t)
+{
+    const uint32_t tiles_per_image = a.tile_w * a.tile_h;
+    t.image_id = blk / tiles_per_image;
+    t.tile_id  = blk % tiles_per_image;
+    t.tile_x   = t.tile_id % a.tile_w;
+    t.tile_y   = t.tile_id / a.tile_w;
+}
+// + its slice of the sorted intersection list, dense layouts: isect_offsets is [I * tiles_per_image], the last tile ends at n_isects
+template <class Args>
+__device__ __forceinline__ void tile_of_block(const Args &a, uint32_t blk, TileCtx &t)
+{
+    tile_coords(a, blk, t);
+    t.range_start = a.isect_offsets[blk];
+    t.range_end   = (blk == a.tile_w * a.tile_h * a.n_images - 1) ? (int32_t)a.n_isects : a.isect_offsets[blk + 1];
+}
+// is the tile masked off (a.masks: [I, tile_h, tile_w] or null)? Two ifs, not `a.masks && !a.masks[..]` returned as a value: the
+// callers branch on it, and this is the shape that leaves their code as it was with the test written in place
+template <class Args>
+__device__ __forceinline__ bool tile_masked(const Args &a, const TileCtx &t)
+{
+    if (a.masks)
+        if (!a.masks[(size_t)t.image_id * (a.tile_w * a.tile_h) + t.tile_id]) return true;
+    return false;
+}
+
+// Which tile does this workgroup own, and which slice of the sorted intersection list? Dense: tile = block. Sparse: tile =
+// active_tiles[block], list slice from the per-active-tile offsets. (The two arms stay written out: the dense arm as
+// tile_of_block(), with tile_x / tile_y formed inside each arm, moves code in every kernel that calls this.)
+template <class Args>
 __device__ __forceinline__ bool tile_context(const Args &a, uint32_t block, TileCtx &t)
 {
     const uint32_t tiles_per_image = a.tile_w * a.tile_h;
@@ -187,6 +225,16 @@ __device__ __forceinline__ bool tile_context(const Args &a, uint32_t block, Tile
     t.tile_y = t.tile_id / a.tile_w;
     return true;
 }
+// Longest tiles first (backward kernels, dense layouts): the tile comes from the workgroup -> tile map that csrc/tile_order.hip
+// builds (Raster3DArgs::tile_order)
+__device__ __forceinline__ bool tile_context_ordered(const Raster3DArgs &a, uint32_t block, TileCtx &t)
+{
+    const uint32_t n_blocks = a.tile_w * a.tile_h * a.n_images;
+    const uint32_t idx      = xcd_remap(block, n_blocks);
+    if (idx >= n_blocks) return false;
+    tile_of_block(a, (uint32_t)a.tile_order[idx], t);
+    return true;
+}
 // The compositing launches' version: segment items (seg_mode 1 / 2), else tile_context minus the tiles that are left to
 // the segment launches. `item` = index of the workgroup's item (modes 1, 2).
 __device__ __forceinline__ bool tile_context_seg(const Raster3DArgs &a, uint32_t block, TileCtx &t, uint32_t &item)
@@ -196,36 +244,27 @@ __device__ __forceinline__ bool tile_context_seg(const Raster3DArgs &a, uint32_t
         if (!tile_context(a, block, t)) return false;
         return !(a.seg_len && !a.sp_active_tiles && (uint32_t)(t.range_end - t.range_start) > a.seg_cut);
     }
-    const int32_t n_items = *a.seg_count;
-    const uint32_t tiles_per_image = a.tile_w * a.tile_h, n_blocks = tiles_per_image * a.n_images;
+    const int32_t n_items   = *a.seg_count;
+    const uint32_t n_blocks = a.tile_w * a.tile_h * a.n_images;
     if ((int32_t)block >= n_items) {
         // compositing pass: the workgroups behind the segment items take the SHORT tiles, whole list, straight into the
         // image (item = ~0) - one launch for everything, the long segments first
         if (a.seg_mode != 2u) return false;
         const uint32_t blk = block - (uint32_t)n_items;
         if (blk >= n_blocks) return false;
-        item       = 0xFFFFFFFFu;
-        t.image_id = blk / tiles_per_image;
-        t.tile_id  = blk % tiles_per_image;
-        t.tile_x   = t.tile_id % a.tile_w;
-        t.tile_y   = t.tile_id / a.tile_w;
-        t.range_start = a.isect_offsets[blk];
-        t.range_end   = (blk == n_blocks - 1) ? (int32_t)a.n_isects : a.isect_offsets[blk + 1];
+        item = 0xFFFFFFFFu;
+        tile_of_block(a, blk, t);
         return (uint32_t)(t.range_end - t.range_start) <= a.seg_cut;
     }
     item = block;
-    const uint32_t blk = (uint32_t)a.seg_items[2 * block];
-    t.image_id = blk / tiles_per_image;
-    t.tile_id  = blk % tiles_per_image;
-    t.tile_x   = t.tile_id % a.tile_w;
-    t.tile_y   = t.tile_id / a.tile_w;
-    const int32_t tile_end = (blk == n_blocks - 1) ? (int32_t)a.n_isects : a.isect_offsets[blk + 1];
+    tile_of_block(a, (uint32_t)a.seg_items[2 * block], t); // the tile's whole list; the item's slice of it:
     t.range_start = a.seg_items[2 * block + 1];
-    t.range_end   = min(t.range_start + (int32_t)a.seg_len, tile_end);
+    t.range_end   = min(t.range_start + (int32_t)a.seg_len, t.range_end);
     return true;
 }
 
-// output row of pixel (lx, ly) of the tile, or -1 when the pixel is not rendered
+// Which output row does the lane of pixel (lx, ly) of the tile write, -1 = the pixel is not rendered? Dense: the pixel's index in
+// the [I, H, W] image. Sparse: pixel_map[first row of the tile + rank of the lane's pixel among the set bits].
 template <class Args>
 __device__ __forceinline__ int64_t pixel_row(const Args &a, const TileCtx &t, uint32_t block, uint32_t lx, uint32_t ly)
 {
@@ -286,23 +325,6 @@ struct RowFill {
 bool raster3d_fwd_m_applies(const Raster3DArgs &a);
 int raster3d_fwd_m_launch(const Raster3DArgs &a, hipStream_t stream);
 
-// ---- longest tiles first: csrc/tile_order.hip builds the order, the backward kernels read it through Raster3DArgs::tile_order ----
-// tile_context() through the order (dense layouts)
-__device__ __forceinline__ bool tile_context_ordered(const Raster3DArgs &a, uint32_t block, TileCtx &t)
-{
-    const uint32_t tiles_per_image = a.tile_w * a.tile_h, n_blocks = tiles_per_image * a.n_images;
-    const uint32_t idx = xcd_remap(block, n_blocks);
-    if (idx >= n_blocks) return false;
-    const uint32_t blk = (uint32_t)a.tile_order[idx];
-    t.image_id = blk / tiles_per_image;
-    t.tile_id  = blk % tiles_per_image;
-    t.tile_x   = t.tile_id % a.tile_w;
-    t.tile_y   = t.tile_id / a.tile_w;
-    t.range_start = a.isect_offsets[blk];
-    t.range_end   = (blk == n_blocks - 1) ? (int32_t)a.n_isects : a.isect_offsets[blk + 1];
-    return true;
-}
-
 // Which backward kernel takes a chunk of nch channels (raster3d_bwd.hip): the reduction kernel, variant T, variant W, or, for
 // wide colour rows (5 .. 32 channels per launch, 16 x 16 tiles, no absgrad), the matrix cores (raster3d_bwd_m.hip).
 enum class BwdKernel { R, T, W, M };
@@ -330,31 +352,23 @@ __device__ __forceinline__ void tile_pixel(uint32_t tid, uint32_t tile_size, uin
 // which is one v_exp_f32 and no multiply by log2(e) / opacity per pixel. Same quantity as the reference's
 // `opac * __expf(-sigma)` (RasterizeToPixels3DGSDevice.cuh:44-56) to ~1e-6 relative.
 constexpr float kLog2e = 1.4426950408889634f;
-__device__ __forceinline__ void stage_gaussian(float x, float y, float opac, float ca, float cb, float cc, float4 &ga,
-                                               float2 &gb)
+
+// One Gaussian's geometry row as every kernel gathers it through flatten_ids: means2d [R, 2], opacities [R], conics [R, 3]
+struct GeoRow {
+    float2 xy;
+    float opac, ca, cb, cc;
+};
+__device__ __forceinline__ GeoRow load_geo_row(const float *means2d, const float *opacities, const float *conics, int32_t g)
 {
-    const float lo = opac > 0.0f ? __log2f(opac) : -INFINITY; // opac <= 0 (or NaN) can never pass the alpha test
-    ga = make_float4(x, y, lo, 0.5f * kLog2e * ca);
-    gb = make_float2(kLog2e * cb, 0.5f * kLog2e * cc);
-}
-// q and the unclamped alpha of the staged Gaussian at offset (dx, dy) = mean - pixel
-__device__ __forceinline__ float staged_q(const float4 &ga, const float2 &gb, float dx, float dy)
-{
-    return fmaf(dx, fmaf(ga.w, dx, gb.x * dy), gb.y * dy * dy);
-}
-__device__ __forceinline__ float staged_alpha_raw(const float4 &ga, float q)
-{
-    return __builtin_amdgcn_exp2f(ga.z - q);
-}
-// The exponent on a (x', y', lo, A | B, C) row with (x', y') = mean - TILE CENTRE and (dx, dy) = (x', y') - (pixel - tile centre):
-// instruction for instruction what staged_f() evaluates on its (ax, ay, lo | nA, nB, nC) row (negation is exact), so that the
-// reduction backward and the query kernels take the alpha test exactly where the forward took it. sigma < 0  <=>  e > ga.z.
-__device__ __forceinline__ float staged_e_offset(const float4 &ga, const float2 &gb, float dx, float dy)
-{
-    return fmaf(dx, fmaf(-gb.x, dy, -ga.w * dx), fmaf(-gb.y * dy, dy, ga.z));
+    GeoRow r;
+    r.xy   = reinterpret_cast<const float2 *>(means2d)[g];
+    r.opac = opacities[g];
+    r.ca = conics[3 * (size_t)g]; r.cb = conics[3 * (size_t)g + 1]; r.cc = conics[3 * (size_t)g + 2];
+    return r;
 }
 
-// ---- staged form of the tile kernels (raster3d_fwd*.hip, raster_indices.hip, variants T / W and the matrix-core backward) ------
+// ---- the staged form: stage_gaussian_f / staged_f are the ONE evaluation of the exponent, for every kernel that takes the alpha
+// test (forward, every backward variant, the query and index kernels) ------
 // With a = mean - c (c = centre of the tile) and a lane's pixel at (u, v) = pixel - c (|u|, |v| <= 7.5, exact in fp32) the
 // exponent of alpha = exp2(e) is evaluated the way the reference does, from the offset d = a - (u, v) = mean - pixel:
 //   e = lo - (A dx^2 + B dx dy + C dy^2) = fma(dx, fma(nB, dy, nA dx), fma(nC dy, dy, lo)),   (nA, nB, nC) = -(A, B, C)
@@ -366,7 +380,8 @@ __device__ __forceinline__ float staged_e_offset(const float4 &ga, const float2 
 // by the backward iff the forward blended it - with another evaluation of the exponent in the backward, a pair within 1.5e-5 of
 // the 1/255 test was taken by one and not by the other (6 of 369 k rows of v_means2d off by up to 6e-3 in the reference's
 // test_rasterize_to_pixels). Their moments stay in the tile-centre frame (u, v); one wave per tile (variant W) shares dx / dy
-// between the four pixels of a lane.
+// between the four pixels of a lane. The reduction backward and the query kernel keep compact LDS rows (ax, ay, lo, nA | nB, nC)
+// and hand staged_f() the same values from there.
 struct StagedRow { // one staged Gaussian in LDS: 48 bytes, read as b128 + b128 + b64 from ONE address register
     v4f p0;        // ax, ay (mean - tile centre), lo (base of the exponent), lo (reject level: e > lo <=> sigma < 0)
     v4f p1;        // nA, nB, nC, colour 2
@@ -447,6 +462,28 @@ __device__ __forceinline__ bool rect_reaches_level(const v4f &p0, const v4f &p1,
     const float q1 = fmaf(dxe, fmaf(A, dxe, B * dys), C * dys * dys);
     const float q2 = fmaf(dxs, fmaf(A, dxs, B * dye), C * dye * dye);
     return fminf(q1, q2) <= p0.w + (7.99435344f + 0.01f); // log2(255)
+}
+
+// The first stage as the kernels call it: the box (x, y) +- (hx, hy) of cull_half_extent() - a row of s_cull; the 2DGS kernels'
+// surfel_cull_box has the same form - against the rectangle, same frame for both. A kernel with a staged row goes on with
+//     if (hit) hit = rect_reaches_level(p0, p1, x, y, rect);
+// at the call site: the two stages wrapped into one function (three shapes tried) changed how the compiler lays out the test
+// in every kernel that used it.
+__device__ __forceinline__ bool box_reaches_rect(float x, float y, float hx, float hy, const WaveRect &r)
+{
+    return (fabsf(x - r.cx) - r.hw <= hx) && (fabsf(y - r.cy) - r.hh <= hy);
+}
+__device__ __forceinline__ bool box_reaches_rect(const float4 &row, const WaveRect &r) // reads the row where it is needed
+{
+    const float4 cu = row;
+    return box_reaches_rect(cu.x, cu.y, cu.z, cu.w, r);
+}
+
+// The scalar loop over a ballot's survivors takes the lowest set bit (bit = ctz(todo)) and clears it: todo &= todo - 1 in ONE
+// scalar instruction (the compiler emits three)
+__device__ __forceinline__ void pop_lowest_bit(uint64_t &todo, int32_t bit)
+{
+    asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit));
 }
 
 } // namespace gsx

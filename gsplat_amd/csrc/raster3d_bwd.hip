@@ -46,8 +46,8 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
     constexpr int BATCH = Cfg::BATCH;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4 *s_ga     = reinterpret_cast<float4 *>(smem_raw);       // x, y, log2(opac), A   (stage_gaussian)
-    float2 *s_gb     = reinterpret_cast<float2 *>(s_ga + BATCH);   // B, C
+    float4 *s_ga     = reinterpret_cast<float4 *>(smem_raw);       // ax, ay, lo, nA: a compact staged row (raster3d.hpp)
+    float2 *s_gb     = reinterpret_cast<float2 *>(s_ga + BATCH);   // nB, nC
     float4 *s_cull   = reinterpret_cast<float4 *>(s_gb + BATCH);   // x, y, half extents of alpha>=1/255
     int32_t *s_id    = reinterpret_cast<int32_t *>(s_cull + BATCH); // flatten id of the row
     int32_t *s_touch = s_id + BATCH;                               // any lane contributed?
@@ -56,9 +56,8 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
 
     TileCtx tc;
     if (!tile_context(a, blockIdx.x, tc)) return;
-    const uint32_t tiles_per_image = a.tile_w * a.tile_h;
-    const uint32_t image_id = tc.image_id, tile_id = tc.tile_id;
-    if (a.masks && !a.masks[(size_t)image_id * tiles_per_image + tile_id]) return;
+    const uint32_t image_id = tc.image_id;
+    if (tile_masked(a, tc)) return;
 
     const uint32_t tid  = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -132,18 +131,17 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
         for (int s = (int)tid; s < BATCH; s += (int)blockDim.x) {
             const int32_t idx = batch_end - s;
             if (idx >= range_start) {
-                const int32_t g  = a.flatten_ids[idx];
-                const float2 xy  = reinterpret_cast<const float2 *>(a.means2d)[g];
-                const float opac = a.opacities[g];
-                const float ca = a.conics[3 * (size_t)g], cb = a.conics[3 * (size_t)g + 1], cc = a.conics[3 * (size_t)g + 2];
+                const int32_t g = a.flatten_ids[idx];
+                const GeoRow r  = load_geo_row(a.means2d, a.opacities, a.conics, g);
                 s_id[s]        = g;
-                float4 ga;
-                float2 gb;
-                stage_gaussian(xy.x - tcx, xy.y - tcy, opac, ca, cb, cc, ga, gb);
-                s_ga[s]        = ga;
-                s_gb[s]        = gb;
-                const float2 he = cull_half_extent(opac, ca, cb, cc);
-                s_cull[s]      = make_float4(ga.x, ga.y, he.x, he.y);
+                const float ax = r.xy.x - tcx, ay = r.xy.y - tcy;
+                v4f p0;
+                float nA, nB, nC;
+                stage_gaussian_f(ax, ay, r.opac, r.ca, r.cb, r.cc, p0, nA, nB, nC);
+                s_ga[s]        = make_float4(ax, ay, p0.z, nA);
+                s_gb[s]        = make_float2(nB, nC);
+                const float2 he = cull_half_extent(r.opac, r.ca, r.cb, r.cc);
+                s_cull[s]      = make_float4(ax, ay, he.x, he.y);
                 const float *c = a.colors + (size_t)g * a.cdim + a.ch_off;
 #pragma unroll
                 for (int k = 0; k < CH; ++k) s_col[s * CH + k] = (k < (int)a.nch) ? c[k] : 0.0f;
@@ -158,8 +156,7 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
           const int32_t tl = j + (int32_t)lane;
           bool hit         = false;
           if (tl >= t_first && tl < batch_size) {
-              const float4 cu = s_cull[tl];
-              hit = (fabsf(cu.x - rect.cx) - rect.hw <= cu.z) && (fabsf(cu.y - rect.cy) - rect.hh <= cu.w);
+              hit = box_reaches_rect(s_cull[tl], rect);
           }
           uint64_t todo = __builtin_amdgcn_ballot_w64(hit);
           while (todo) { // scalar loop over the survivors, back to front
@@ -169,9 +166,9 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
             // every contribution exactly 0 and leaves T / buffer unchanged (1/(1-0) == 1 exactly).
             const float4 ga = s_ga[t];
             const float2 gb = s_gb[t];
-            const float dx = ga.x - px;
+            const float dx = ga.x - px; // mean - pixel, as staged_f() forms it: the moments below are taken over it
             const float dy = ga.y - py;
-            const float e    = staged_e_offset(ga, gb, dx, dy);
+            const float e    = staged_f(v4f{ga.x, ga.y, ga.z, ga.z}, ga.w, gb.x, gb.y, px, py);
             const float ov_r = __builtin_amdgcn_exp2f(e); // opac * exp(-sigma), unclamped
             // lanes outside the image have bin_final = -1 and can never be valid; e > lo <=> sigma < 0
             const bool valid = (batch_end - t <= bin_final) && !(e > ga.z) && !(fminf(kMaxAlpha, ov_r) < kAlphaThreshold);
@@ -202,7 +199,8 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
                 loc[CH + 4]     = wdy;
                 loc[CH + 5]     = v_sigma;
                 if constexpr (ABS) {
-                    // |conic . (wdx, wdy)| with conic = (2A, B; B, 2C) / log2(e); the 1/log2(e) is applied at flush
+                    // |conic . (wdx, wdy)| with conic = -(2 nA, nB; nB, 2 nC) / log2(e) (the sign drops out under |.|); the
+                    // 1/log2(e) is applied at flush
                     loc[CH + 6] = fabsf(2.0f * ga.w * wdx + gb.x * wdy);
                     loc[CH + 7] = fabsf(gb.x * wdx + 2.0f * gb.y * wdy);
                 }
@@ -235,7 +233,7 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
         // flush, transposed: element e of the batch's [batch_size][NCOL] gradient block -> (Gaussian s, column c);
         // consecutive lanes -> consecutive floats of one AoS row. Moments become gradients here (linear maps):
         //   v_xy = Q (S_x, S_y), v_conic = (S_xx/2, S_xy, S_yy/2), v_opacity = sum vis*v_alpha = -S_w / opacity
-        // (a touched Gaussian has opacity >= 1/255), with Q = (2A, B; B, 2C) / log2(e) and opacity = exp2(lo) from
+        // (a touched Gaussian has opacity >= 1/255), with Q = -(2 nA, nB; nB, 2 nC) / log2(e) and opacity = exp2(lo) from
         // the staged form.
         constexpr float kInvLog2e = 1.0f / kLog2e;
         constexpr int GEO  = 6 + (ABS ? 2 : 0);
@@ -250,7 +248,7 @@ __global__ void __launch_bounds__(256) raster3d_bwd_kernel(const Raster3DArgs a)
                 const float4 ga = s_ga[s];
                 const float2 gb = s_gb[s];
                 const float sx = row[CH + 3], sy = row[CH + 4];
-                val = kInvLog2e * ((c == 0) ? (2.0f * ga.w * sx + gb.x * sy) : (gb.x * sx + 2.0f * gb.y * sy));
+                val = -kInvLog2e * ((c == 0) ? (2.0f * ga.w * sx + gb.x * sy) : (gb.x * sx + 2.0f * gb.y * sy));
             } else if (c < 5) {
                 const float m = row[CH + c - 2];
                 val           = (c == 3) ? m : 0.5f * m;
@@ -351,9 +349,8 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
         if (!tile_context_ordered(a, blockIdx.x, tc)) return;
     } else if (!tile_context_seg(a, blockIdx.x, tc, seg_item)) return;
     const bool in_segment = a.seg_mode != 0u && seg_item != 0xFFFFFFFFu; // a slice of a long tile list (raster3d_seg.hip)
-    const uint32_t tiles_per_image = a.tile_w * a.tile_h;
-    const uint32_t image_id = tc.image_id, tile_id = tc.tile_id;
-    if (a.masks && !a.masks[(size_t)image_id * tiles_per_image + tile_id]) return;
+    const uint32_t image_id = tc.image_id;
+    if (tile_masked(a, tc)) return;
 
     const uint32_t tid  = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -512,16 +509,14 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
         for (int s = (int)tid; s < BATCH; s += (int)blockDim.x) {
             const int32_t idx = batch_end - s;
             if (idx >= range_start) {
-                const int32_t g  = a.flatten_ids[idx];
-                const float2 xy  = reinterpret_cast<const float2 *>(a.means2d)[g];
-                const float opac = a.opacities[g];
-                const float ca = a.conics[3 * (size_t)g], cb = a.conics[3 * (size_t)g + 1], cc = a.conics[3 * (size_t)g + 2];
+                const int32_t g = a.flatten_ids[idx];
+                const GeoRow r  = load_geo_row(a.means2d, a.opacities, a.conics, g);
                 s_id[s]        = g;
-                const float ax = xy.x - tile_cx, ay = xy.y - tile_cy;
+                const float ax = r.xy.x - tile_cx, ay = r.xy.y - tile_cy;
                 v4f p0;
                 float nA, nB, nC;
-                stage_gaussian_f(ax, ay, opac, ca, cb, cc, p0, nA, nB, nC);
-                const float2 he = cull_half_extent(opac, ca, cb, cc);
+                stage_gaussian_f(ax, ay, r.opac, r.ca, r.cb, r.cc, p0, nA, nB, nC);
+                const float2 he = cull_half_extent(r.opac, r.ca, r.cb, r.cc);
                 s_cull[s]      = make_float4(ax, ay, he.x, he.y);
                 const float *c = a.colors + (size_t)g * a.cdim + a.ch_off;
                 float cv[4];
@@ -541,14 +536,14 @@ raster3d_bwd_t_kernel(Raster3DArgs a)
           bool hit         = false;
           if (tl >= t_first && tl < batch_size) {
               const float4 cu = s_cull[tl];
-              hit = (fabsf(cu.x - rect.cx) - rect.hw <= cu.z) && (fabsf(cu.y - rect.cy) - rect.hh <= cu.w);
+              hit = box_reaches_rect(cu.x, cu.y, cu.z, cu.w, rect);
               if (hit) hit = rect_reaches_level(s_st[tl].p0, s_st[tl].p1, cu.x, cu.y, rect); // exact second stage
           }
           uint64_t todo = __builtin_amdgcn_ballot_w64(hit);
           while (todo) {
             const int32_t bit = (int32_t)__builtin_ctzll(todo);
             const int32_t t   = j + bit;
-            asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit)); // todo &= todo - 1 in ONE scalar instruction (the compiler emits three)
+            pop_lowest_bit(todo, bit);
             const v4f p0 = s_st[t].p0;
             const v4f p1 = s_st[t].p1;
             // the colours ride along with the two reads above (one address register, their latency under the exponent's
@@ -718,7 +713,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
 
     TileCtx tc;
     if (a.tile_order ? !tile_context_ordered(a, blockIdx.x, tc) : !tile_context(a, blockIdx.x, tc)) return;
-    if (a.masks && !a.masks[(size_t)tc.image_id * (a.tile_w * a.tile_h) + tc.tile_id]) return;
+    if (tile_masked(a, tc)) return;
     const int32_t range_start = tc.range_start;
     if (tc.range_end <= range_start) return;
 
@@ -907,16 +902,14 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
     // Staging is wave-private, so its two dependent global reads (list entry -> the Gaussian's rows) would sit in front of every
     // batch with nothing of this wave to hide them: the rows of batch b + 1 and the list entries of batch b + 2 are requested
     // before batch b is walked.
-    struct Fetched { float2 xy; float opac, ca, cb, cc, cv[4]; };
+    struct Fetched { GeoRow r; float cv[4]; };
     auto entry_of = [&](int32_t b) -> int32_t { // flatten id of this lane's entry of batch b, -1 = none
         const int32_t idx = range_end - 1 - BATCH * b - (int32_t)lane;
         return (b < n_batches && idx >= range_start) ? a.flatten_ids[idx] : -1;
     };
     auto fetch = [&](int32_t g, Fetched &f) {
         if (g < 0) return;
-        f.xy   = reinterpret_cast<const float2 *>(a.means2d)[g];
-        f.opac = a.opacities[g];
-        f.ca = a.conics[3 * (size_t)g]; f.cb = a.conics[3 * (size_t)g + 1]; f.cc = a.conics[3 * (size_t)g + 2];
+        f.r = load_geo_row(a.means2d, a.opacities, a.conics, g);
         const float *cp = a.colors + (size_t)g * a.cdim + a.ch_off;
 #pragma unroll
         for (int k = 0; k < 4; ++k) f.cv[k] = (k < CH && k < (int)a.nch) ? cp[k] : 0.0f;
@@ -933,8 +926,8 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
             const int32_t g = g_cur;
             const Fetched f = f_cur;
             if (g >= 0) {
-                const float opac = f.opac, ca = f.ca, cb = f.cb, cc = f.cc;
-                const float ax = f.xy.x - tile_cx, ay = f.xy.y - tile_cy;
+                const float opac = f.r.opac, ca = f.r.ca, cb = f.r.cb, cc = f.r.cc;
+                const float ax = f.r.xy.x - tile_cx, ay = f.r.xy.y - tile_cy;
                 v4f p0;
                 float nA, nB, nC;
                 stage_gaussian_f(ax, ay, opac, ca, cb, cc, p0, nA, nB, nC);
@@ -949,8 +942,8 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
                 for (int q = 0; q < 4; ++q) {
                     WaveRect r;
                     r.cx = (q & 1) ? 4.0f : -4.0f; r.cy = (q >> 1) ? 4.0f : -4.0f; r.hw = 3.5f; r.hh = 3.5f; r.any = true;
-                    bool hit = idx <= qmax[q] && (fabsf(ax - r.cx) - r.hw <= he.x) && (fabsf(ay - r.cy) - r.hh <= he.y);
-                    if (hit) hit = rect_reaches_level(p0, p1, ax, ay, r);
+                    bool hit = idx <= qmax[q] && box_reaches_rect(ax, ay, he.x, he.y, r);
+                    if (hit) hit = rect_reaches_level(p0, p1, ax, ay, r); // exact second stage
                     hitmask |= hit ? (1 << q) : 0;
                 }
             }
@@ -964,7 +957,7 @@ __device__ __forceinline__ void raster3d_bwd_w_body(const Raster3DArgs &a)
         uint64_t todo          = __builtin_amdgcn_ballot_w64(hitmask != 0);
         while (todo) {
             const int32_t t = (int32_t)__builtin_ctzll(todo);
-            asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(t)); // todo &= todo - 1 in one scalar instruction
+            pop_lowest_bit(todo, t);
             const int qm = __builtin_amdgcn_readlane(hitmask, t);
             const v4f p0 = s_st[t].p0;
             const v4f p1 = s_st[t].p1;
@@ -1063,9 +1056,8 @@ BwdKernel raster3d_bwd_kernel(uint32_t tile_size, uint32_t nch, bool has_abs)
 template <int CH, bool ABS>
 static int launch_bwd(const Raster3DArgs &a, BwdKernel kernel, hipStream_t stream)
 {
-    const uint32_t n_blocks = a.sp_active_tiles ? a.n_active : a.tile_w * a.tile_h * a.n_images;
-    if (n_blocks == 0 || a.n_isects == 0) return GSX_OK;
-    const uint32_t grid  = ((n_blocks + 7u) / 8u) * 8u;
+    const uint32_t grid = tile_grid(a);
+    if (grid == 0 || a.n_isects == 0) return GSX_OK;
     if constexpr (CH <= 4) {
         if (kernel == BwdKernel::W) {
             if constexpr (ABS) raster3d_bwd_w_abs_kernel<CH><<<dim3(grid), dim3(64), BwdWCfg<CH, true>::smem, stream>>>(a);
@@ -1090,7 +1082,7 @@ static int launch_bwd(const Raster3DArgs &a, BwdKernel kernel, hipStream_t strea
 // variant T over a segment item list + the short tiles behind it (raster3d_seg.hip); a.nch <= 4, tile size 16, no absgrad
 int raster3d_bwd_t_launch_items(const Raster3DArgs &a, hipStream_t stream)
 {
-    const uint32_t grid = ((a.seg_grid + 7u) / 8u) * 8u;
+    const uint32_t grid = xcd_grid(a.seg_grid);
     if (grid == 0) return GSX_OK;
     with_channels4(a.nch, [&](auto ch) {
         raster3d_bwd_t_kernel<ch()><<<dim3(grid), dim3(256), BwdTCfg<ch()>::smem, stream>>>(a);

@@ -81,7 +81,7 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
 
     TileCtx tc;
     if (a.tile_order ? !tile_context_ordered(a, blockIdx.x, tc) : !tile_context(a, blockIdx.x, tc)) return;
-    if (a.masks && !a.masks[(size_t)tc.image_id * (a.tile_w * a.tile_h) + tc.tile_id]) return;
+    if (tile_masked(a, tc)) return;
     const int32_t range_start = tc.range_start;
     if (tc.range_end <= range_start) return;
 
@@ -196,15 +196,13 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
             if (idx >= range_start) {
                 const int32_t g = a.flatten_ids[idx];
                 if (part == 0) {
-                    const float2 xy  = reinterpret_cast<const float2 *>(a.means2d)[g];
-                    const float opac = a.opacities[g];
-                    const float ca = a.conics[3 * (size_t)g], cb = a.conics[3 * (size_t)g + 1], cc = a.conics[3 * (size_t)g + 2];
+                    const GeoRow r = load_geo_row(a.means2d, a.opacities, a.conics, g);
                     s_id[s]        = g;
-                    const float ax = xy.x - tile_cx, ay = xy.y - tile_cy;
+                    const float ax = r.xy.x - tile_cx, ay = r.xy.y - tile_cy;
                     v4f p0;
                     float nA, nB, nC;
-                    stage_gaussian_f(ax, ay, opac, ca, cb, cc, p0, nA, nB, nC);
-                    const float2 he = cull_half_extent(opac, ca, cb, cc);
+                    stage_gaussian_f(ax, ay, r.opac, r.ca, r.cb, r.cc, p0, nA, nB, nC);
+                    const float2 he = cull_half_extent(r.opac, r.ca, r.cb, r.cc);
                     s_cull[s]      = make_float4(ax, ay, he.x, he.y);
                     s_st[s].p0     = p0;
                     s_st[s].p1     = v4f{nA, nB, nC, 0.0f};
@@ -226,7 +224,7 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
         bool hit = false;
         if ((int32_t)lane >= t_first && (int32_t)lane < batch_size) {
             const float4 cu = s_cull[lane];
-            hit = (fabsf(cu.x - rect.cx) - rect.hw <= cu.z) && (fabsf(cu.y - rect.cy) - rect.hh <= cu.w);
+            hit = box_reaches_rect(cu.x, cu.y, cu.z, cu.w, rect);
             if (hit) hit = rect_reaches_level(s_st[lane].p0, s_st[lane].p1, cu.x, cu.y, rect); // exact second stage
         }
         uint64_t todo = __builtin_amdgcn_ballot_w64(hit);
@@ -401,9 +399,8 @@ raster3d_bwd_m_kernel(const Raster3DArgs a)
 
 int raster3d_bwd_m_launch(const Raster3DArgs &a, hipStream_t stream)
 {
-    const uint32_t n_blocks = a.sp_active_tiles ? a.n_active : a.tile_w * a.tile_h * a.n_images;
-    if (n_blocks == 0 || a.n_isects == 0) return GSX_OK;
-    const uint32_t grid = ((n_blocks + 7u) / 8u) * 8u;
+    const uint32_t grid = tile_grid(a);
+    if (grid == 0 || a.n_isects == 0) return GSX_OK;
     if (a.nch <= 16) raster3d_bwd_m_kernel<1><<<dim3(grid), dim3(256), BwdMCfg<1>::smem, stream>>>(a);
     else raster3d_bwd_m_kernel<2><<<dim3(grid), dim3(256), BwdMCfg<2>::smem, stream>>>(a);
     return check_launch("raster3d_bwd_m");

@@ -31,8 +31,7 @@ __global__ void __launch_bounds__(256) raster3d_fwd_kernel(const Raster3DArgs a)
     // what this workgroup is: a whole tile (also the short tiles of a compositing-pass launch), or a segment in the
     // transmittance / compositing pass
     const uint32_t seg_mode = seg_item == 0xFFFFFFFFu ? 0u : a.seg_mode;
-    const uint32_t tiles_per_image = a.tile_w * a.tile_h;
-    const uint32_t image_id = tc.image_id, tile_id = tc.tile_id;
+    const uint32_t image_id = tc.image_id;
     const uint32_t tid      = threadIdx.x;
 
     uint32_t lx, ly;
@@ -48,7 +47,9 @@ __global__ void __launch_bounds__(256) raster3d_fwd_kernel(const Raster3DArgs a)
     const float *bg = a.backgrounds ? a.backgrounds + (size_t)image_id * a.cdim + a.ch_off : nullptr;
 
     // masked-off tile: background colour, zero alpha, last_id 0 (reference Fwd.cu:141-159)
-    if (a.masks && !a.masks[(size_t)image_id * tiles_per_image + tile_id]) {
+    // (spelled out, not tile_masked(): in front of this many-armed block the helper's branch form moves the arms of the
+    // non-segment instantiations around)
+    if (a.masks && !a.masks[(size_t)image_id * (a.tile_w * a.tile_h) + tc.tile_id]) {
         if constexpr (PRE) {
             a.seg_T[(size_t)seg_item * 256 + tid]   = 1.0f;
             a.seg_out[(size_t)seg_item * 256 + tid] = 0.0f;
@@ -109,15 +110,13 @@ __global__ void __launch_bounds__(256) raster3d_fwd_kernel(const Raster3DArgs a)
         for (int s = (int)tid; s < kBatch; s += (int)blockDim.x) {
             const int32_t idx = batch_start + s;
             if (idx < range_end) {
-                const int32_t g  = a.flatten_ids[idx];
-                const float2 xy  = reinterpret_cast<const float2 *>(a.means2d)[g];
-                const float opac = a.opacities[g];
-                const float ca = a.conics[3 * (size_t)g], cb = a.conics[3 * (size_t)g + 1], cc = a.conics[3 * (size_t)g + 2];
-                const float ax = xy.x - cx, ay = xy.y - cy;
+                const int32_t g = a.flatten_ids[idx];
+                const GeoRow r  = load_geo_row(a.means2d, a.opacities, a.conics, g);
+                const float ax = r.xy.x - cx, ay = r.xy.y - cy;
                 v4f p0;
                 float nA, nB, nC;
-                stage_gaussian_f(ax, ay, opac, ca, cb, cc, p0, nA, nB, nC);
-                const float2 he = cull_half_extent(opac, ca, cb, cc);
+                stage_gaussian_f(ax, ay, r.opac, r.ca, r.cb, r.cc, p0, nA, nB, nC);
+                const float2 he = cull_half_extent(r.opac, r.ca, r.cb, r.cc);
                 s_cull[s]       = make_float4(ax, ay, he.x, he.y);
                 const float *c  = a.colors + (size_t)g * a.cdim + a.ch_off;
                 float cv[CH > 4 ? CH : 4];
@@ -147,14 +146,14 @@ __global__ void __launch_bounds__(256) raster3d_fwd_kernel(const Raster3DArgs a)
             bool hit         = false;
             if (tl < batch_size) {
                 const float4 cu = s_cull[tl];
-                hit = (fabsf(cu.x - rect.cx) - rect.hw <= cu.z) && (fabsf(cu.y - rect.cy) - rect.hh <= cu.w);
+                hit = box_reaches_rect(cu.x, cu.y, cu.z, cu.w, rect);
                 if (hit) hit = rect_reaches_level(s_st[tl].p0, s_st[tl].p1, cu.x, cu.y, rect); // exact second stage
             }
             uint64_t todo = __builtin_amdgcn_ballot_w64(hit);
             while (todo) {
                 const int32_t bit = (int32_t)__builtin_ctzll(todo);
                 const int32_t t   = j + bit;
-                asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit)); // todo &= todo - 1 in one scalar instruction
+                pop_lowest_bit(todo, bit);
 
                 const v4f p0 = s_st[t].p0;
                 const v4f p1 = s_st[t].p1;
@@ -224,9 +223,8 @@ __global__ void __launch_bounds__(256) raster3d_fwd_kernel(const Raster3DArgs a)
 template <int CH>
 static int launch_fwd(const Raster3DArgs &a, hipStream_t stream)
 {
-    const uint32_t n_blocks = a.seg_mode ? a.seg_grid : (a.sp_active_tiles ? a.n_active : a.tile_w * a.tile_h * a.n_images);
-    if (n_blocks == 0) return GSX_OK;
-    const uint32_t grid   = ((n_blocks + 7u) / 8u) * 8u; // xcd_remap needs a multiple of 8
+    const uint32_t grid = a.seg_mode ? xcd_grid(a.seg_grid) : tile_grid(a);
+    if (grid == 0) return GSX_OK;
     const uint32_t block  = a.tile_size <= 8 ? 64u : 256u;
     const size_t smem     = kBatch * (sizeof(StagedRow) + sizeof(float4) + sizeof(float) * (CH > 4 ? CH - 4 : 0));
     hipLaunchKernelGGL(raster3d_fwd_kernel<CH>, dim3(grid), dim3(block), smem, stream, a);
@@ -236,7 +234,7 @@ static int launch_fwd(const Raster3DArgs &a, hipStream_t stream)
 // pre-pass of the segmented backward (<= 4 channels: the backward's variant T): a.seg_mode = 1 item list, grid a.seg_grid
 int raster3d_bwd_prepass_launch(const Raster3DArgs &a, hipStream_t stream)
 {
-    const uint32_t grid = ((a.seg_grid + 7u) / 8u) * 8u;
+    const uint32_t grid = xcd_grid(a.seg_grid);
     if (grid == 0) return GSX_OK;
     const size_t smem = kBatch * (sizeof(StagedRow) + sizeof(float4));
     with_channels4(a.nch, [&](auto ch) {

@@ -50,7 +50,6 @@ __global__ void __launch_bounds__(256) raster3d_fwd_m_kernel(const Raster3DArgs 
 
     TileCtx tc;
     if (!tile_context(a, blockIdx.x, tc)) return; // uniform for the whole workgroup
-    const uint32_t tiles_per_image = a.tile_w * a.tile_h;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     uint32_t lx, ly;
     tile_pixel(tid, 16u, lx, ly);
@@ -62,7 +61,7 @@ __global__ void __launch_bounds__(256) raster3d_fwd_m_kernel(const Raster3DArgs 
     const float *bg = a.backgrounds ? a.backgrounds + (size_t)tc.image_id * a.cdim + a.ch_off : nullptr;
 
     // masked-off tile: background colour, zero alpha, last_id 0 (reference Fwd.cu:141-159)
-    if (a.masks && !a.masks[(size_t)tc.image_id * tiles_per_image + tc.tile_id]) {
+    if (tile_masked(a, tc)) {
         if (inside) {
             for (uint32_t k = 0; k < a.nch; ++k) a.render_colors[pix * a.cdim + a.ch_off + k] = bg ? bg[k] : 0.0f;
             if (a.first_chunk) {
@@ -98,14 +97,12 @@ __global__ void __launch_bounds__(256) raster3d_fwd_m_kernel(const Raster3DArgs 
             if (idx < range_end) {
                 const int32_t g = a.flatten_ids[idx];
                 if (part == 0) {
-                    const float2 xy  = reinterpret_cast<const float2 *>(a.means2d)[g];
-                    const float opac = a.opacities[g];
-                    const float ca = a.conics[3 * (size_t)g], cb = a.conics[3 * (size_t)g + 1], cc = a.conics[3 * (size_t)g + 2];
-                    const float ax = xy.x - tile_cx, ay = xy.y - tile_cy;
+                    const GeoRow r = load_geo_row(a.means2d, a.opacities, a.conics, g);
+                    const float ax = r.xy.x - tile_cx, ay = r.xy.y - tile_cy;
                     v4f p0;
                     float nA, nB, nC;
-                    stage_gaussian_f(ax, ay, opac, ca, cb, cc, p0, nA, nB, nC);
-                    const float2 he = cull_half_extent(opac, ca, cb, cc);
+                    stage_gaussian_f(ax, ay, r.opac, r.ca, r.cb, r.cc, p0, nA, nB, nC);
+                    const float2 he = cull_half_extent(r.opac, r.ca, r.cb, r.cc);
                     s_cull[s]  = make_float4(ax, ay, he.x, he.y);
                     s_st[s].p0 = p0;
                     s_st[s].p1 = v4f{nA, nB, nC, 0.0f};
@@ -132,7 +129,7 @@ __global__ void __launch_bounds__(256) raster3d_fwd_m_kernel(const Raster3DArgs 
         bool hit = false;
         if ((int32_t)lane < batch_size) {
             const float4 cu = s_cull[lane];
-            hit = (fabsf(cu.x - rect.cx) - rect.hw <= cu.z) && (fabsf(cu.y - rect.cy) - rect.hh <= cu.w);
+            hit = box_reaches_rect(cu.x, cu.y, cu.z, cu.w, rect);
             if (hit) hit = rect_reaches_level(s_st[lane].p0, s_st[lane].p1, cu.x, cu.y, rect); // exact second stage
         }
         const uint64_t todo = __builtin_amdgcn_ballot_w64(hit);
@@ -226,9 +223,8 @@ bool raster3d_fwd_m_applies(const Raster3DArgs &a)
 }
 int raster3d_fwd_m_launch(const Raster3DArgs &a, hipStream_t stream)
 {
-    const uint32_t n_blocks = a.sp_active_tiles ? a.n_active : a.tile_w * a.tile_h * a.n_images;
-    if (n_blocks == 0) return GSX_OK;
-    const uint32_t grid = ((n_blocks + 7u) / 8u) * 8u; // xcd_remap needs a multiple of 8
+    const uint32_t grid = tile_grid(a);
+    if (grid == 0) return GSX_OK;
     if (a.nch <= 16) raster3d_fwd_m_kernel<1><<<dim3(grid), dim3(256), FwdMCfg<1>::smem, stream>>>(a);
     else raster3d_fwd_m_kernel<2><<<dim3(grid), dim3(256), FwdMCfg<2>::smem, stream>>>(a);
     return check_launch("raster3d_fwd_m");

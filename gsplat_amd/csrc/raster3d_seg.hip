@@ -171,10 +171,8 @@ __global__ void __launch_bounds__(256) seg_bwd_from_fwd_kernel(const Raster3DArg
     if (li >= pf.hdr->n_long) return;
     const uint32_t blk = (uint32_t)pf.longs[3 * li];
     const int32_t s0 = pf.longs[3 * li + 1], n_seg = pf.longs[3 * li + 2];
-    const uint32_t tiles_per_image = a.tile_w * a.tile_h;
     TileCtx tc;
-    tc.image_id = blk / tiles_per_image; tc.tile_id = blk % tiles_per_image;
-    tc.tile_x = tc.tile_id % a.tile_w; tc.tile_y = tc.tile_id / a.tile_w;
+    tile_coords(a, blk, tc);
     tc.range_start = tc.range_end = 0;
     const uint32_t tid = threadIdx.x;
     uint32_t lx, ly;
@@ -221,10 +219,8 @@ __global__ void __launch_bounds__(256) seg_combine_kernel(const Raster3DArgs a, 
     if (li >= p.hdr->n_long) return;
     const uint32_t blk = (uint32_t)p.longs[3 * li];
     const int32_t s0 = p.longs[3 * li + 1], n_seg = p.longs[3 * li + 2];
-    const uint32_t tiles_per_image = a.tile_w * a.tile_h;
     TileCtx tc;
-    tc.image_id = blk / tiles_per_image; tc.tile_id = blk % tiles_per_image;
-    tc.tile_x = tc.tile_id % a.tile_w; tc.tile_y = tc.tile_id / a.tile_w;
+    tile_coords(a, blk, tc);
     tc.range_start = tc.range_end = 0;
     const uint32_t tid = threadIdx.x;
     uint32_t lx, ly;
@@ -244,7 +240,7 @@ __global__ void __launch_bounds__(256) seg_combine_kernel(const Raster3DArgs a, 
         last            = l >= 0 ? l : last;
     }
     const float *bg   = a.backgrounds ? a.backgrounds + (size_t)tc.image_id * a.cdim + a.ch_off : nullptr;
-    const bool masked = a.masks && !a.masks[(size_t)tc.image_id * tiles_per_image + tc.tile_id];
+    const bool masked = a.masks && !a.masks[(size_t)tc.image_id * (a.tile_w * a.tile_h) + tc.tile_id];
     for (uint32_t c = 0; c < a.nch; ++c) {
         float acc = 0.0f;
         for (int32_t k = 0; k < n_seg; ++k) acc += p.out[((size_t)(s0 + k) * planes + c) * 256 + tid]; // front to back
@@ -410,7 +406,7 @@ static int raster3d_bwd_seg_impl(
     }
     // the slices first, the short tiles behind them. The short-tile range must hold round8(n_blocks) workgroups whatever the
     // device-side item count is (xcd_remap is a bijection over round8(n_blocks) slots only)
-    a.seg_mode = 2; a.seg_grid = p.max_items + ((n_blocks + 7u) / 8u) * 8u;
+    a.seg_mode = 2; a.seg_grid = p.max_items + xcd_grid(n_blocks);
     rc = raster3d_bwd_t_launch_items(a, s);
     if (rc != GSX_OK) return rc;
     return check_launch("raster3d_bwd_seg");

@@ -39,9 +39,9 @@ template <int MODE>
 __global__ void __launch_bounds__(256) raster3d_query_kernel(const QueryArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4 *s_ga   = reinterpret_cast<float4 *>(smem_raw);        // x, y, log2(opac), A
+    float4 *s_ga   = reinterpret_cast<float4 *>(smem_raw);        // ax, ay, lo, nA: a compact staged row (raster3d.hpp)
     float4 *s_cull = s_ga + kQBatch;
-    float2 *s_gb   = reinterpret_cast<float2 *>(s_cull + kQBatch); // B, C
+    float2 *s_gb   = reinterpret_cast<float2 *>(s_cull + kQBatch); // nB, nC
     int32_t *s_id  = reinterpret_cast<int32_t *>(s_gb + kQBatch);  // local Gaussian id
     // MODE == kQTop: per-pixel top-K scratch, [K][blockDim] so that a lane's slots sit in its own bank column
     float *s_w     = reinterpret_cast<float *>(s_id + kQBatch);
@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(256) raster3d_query_kernel(const QueryArgs a)
     tile_pixel(tid, a.tile_size, lx, ly);
     const int64_t prow = pixel_row(a, tc, blockIdx.x, lx, ly);
     const bool inside  = prow >= 0;
-    // the tile-centre frame of the compositing kernels: the alpha test is theirs, bit for bit (raster3d.hpp: staged_e_offset)
+    // the tile-centre frame of the compositing kernels: the alpha test is theirs, bit for bit (raster3d.hpp: staged_f)
     const float half_q = 0.5f * (float)a.tile_size;
     const float tcx = (float)(tc.tile_x * a.tile_size) + half_q, tcy = (float)(tc.tile_y * a.tile_size) + half_q;
     const float px = (float)lx + 0.5f - half_q, py = (float)ly + 0.5f - half_q; // pixel centre - tile centre
@@ -83,17 +83,16 @@ __global__ void __launch_bounds__(256) raster3d_query_kernel(const QueryArgs a)
         for (int s = (int)tid; s < kQBatch; s += (int)nthr) {
             const int32_t idx = batch_start + s;
             if (idx < range_end) {
-                const int32_t g  = a.flatten_ids[idx];
-                const float2 xy  = reinterpret_cast<const float2 *>(a.means2d)[g];
-                const float opac = a.opacities[g];
-                const float ca = a.conics[3 * (size_t)g], cb = a.conics[3 * (size_t)g + 1], cc = a.conics[3 * (size_t)g + 2];
-                float4 ga;
-                float2 gb;
-                stage_gaussian(xy.x - tcx, xy.y - tcy, opac, ca, cb, cc, ga, gb);
-                s_ga[s] = ga;
-                s_gb[s] = gb;
-                const float2 he = cull_half_extent(opac, ca, cb, cc);
-                s_cull[s]       = make_float4(ga.x, ga.y, he.x, he.y);
+                const int32_t g = a.flatten_ids[idx];
+                const GeoRow r  = load_geo_row(a.means2d, a.opacities, a.conics, g);
+                const float ax = r.xy.x - tcx, ay = r.xy.y - tcy;
+                v4f p0;
+                float nA, nB, nC;
+                stage_gaussian_f(ax, ay, r.opac, r.ca, r.cb, r.cc, p0, nA, nB, nC);
+                s_ga[s] = make_float4(ax, ay, p0.z, nA);
+                s_gb[s] = make_float2(nB, nC);
+                const float2 he = cull_half_extent(r.opac, r.ca, r.cb, r.cc);
+                s_cull[s]       = make_float4(ax, ay, he.x, he.y);
                 s_id[s]         = a.n_per_image ? (int32_t)((uint32_t)g % a.n_per_image) : g;
             }
         }
@@ -104,8 +103,7 @@ __global__ void __launch_bounds__(256) raster3d_query_kernel(const QueryArgs a)
             const int32_t tl = j + (int32_t)lane;
             bool hit         = false;
             if (tl < batch_size) {
-                const float4 cu = s_cull[tl];
-                hit = (fabsf(cu.x - rect.cx) - rect.hw <= cu.z) && (fabsf(cu.y - rect.cy) - rect.hh <= cu.w);
+                hit = box_reaches_rect(s_cull[tl], rect);
             }
             uint64_t todo = __builtin_amdgcn_ballot_w64(hit);
             while (todo) {
@@ -113,8 +111,7 @@ __global__ void __launch_bounds__(256) raster3d_query_kernel(const QueryArgs a)
                 todo &= todo - 1;
                 const float4 ga = s_ga[t];
                 const float2 gb = s_gb[t];
-                const float dx = ga.x - px, dy = ga.y - py;
-                const float e     = staged_e_offset(ga, gb, dx, dy);
+                const float e     = staged_f(v4f{ga.x, ga.y, ga.z, ga.z}, ga.w, gb.x, gb.y, px, py);
                 const float alpha = fminf(kMaxAlpha, __builtin_amdgcn_exp2f(e));
                 const bool neg    = e > ga.z; // sigma < 0
                 if constexpr (MODE == kQStats) {
@@ -210,9 +207,8 @@ __global__ void __launch_bounds__(256) raster3d_query_kernel(const QueryArgs a)
 template <int MODE>
 static int launch_query(const QueryArgs &a, hipStream_t stream)
 {
-    const uint32_t n_blocks = a.sp_active_tiles ? a.n_active : a.tile_w * a.tile_h * a.n_images;
-    if (n_blocks == 0) return GSX_OK;
-    const uint32_t grid  = ((n_blocks + 7u) / 8u) * 8u;
+    const uint32_t grid  = tile_grid(a);
+    if (grid == 0) return GSX_OK;
     const uint32_t block = a.tile_size <= 8 ? 64u : 256u;
     size_t smem = kQBatch * (2 * sizeof(float4) + sizeof(float2) + sizeof(int32_t));
     if (MODE == kQTop) {

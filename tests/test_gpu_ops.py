@@ -624,6 +624,16 @@ def test_rasterize_tile_sizes(G, O, tile_size):
     _raster_case(G, O, N=3000, C=1, W=150, H=100, tile_size=tile_size, D=3, seed=20 + tile_size, bg=True)
 
 
+@pytest.mark.parametrize("absgrad,tile_size,D", [
+    (False, 8, 1), (False, 12, 2), (False, 8, 3), (False, 12, 4), (False, 8, 5), (False, 12, 16), (False, 8, 32),
+    (True, 12, 1), (True, 8, 2), (True, 12, 3), (True, 8, 4), (True, 12, 7), (True, 8, 12), (True, 12, 20)])
+def test_rasterize_reduction_backward_every_instantiation(G, O, absgrad, tile_size, D):
+    """The reduction backward (csrc/raster3d_bwd.hip: raster3d_bwd_kernel<CH, ABS>) takes every tile size other than 16: each of
+    its channel widths (1, 2, 3, 4, 8, 16, 32 hold D) with and without absgrad, in its 64-thread block (tile size 8) and its
+    256-thread block (tile size 12, 112 surplus threads), on two images of 40 x 24 pixels (partial tiles on both edges)."""
+    _raster_case(G, O, N=64, C=2, W=40, H=24, tile_size=tile_size, D=D, seed=50 + D + tile_size, bg=(D % 2 == 1), absgrad=absgrad)
+
+
 def test_rasterize_masks_absgrad_packed(G, O):
     _raster_case(G, O, N=6000, C=2, W=200, H=136, tile_size=16, D=3, seed=31, bg=True, masks=True, absgrad=True)
     _raster_case(G, O, N=6000, C=2, W=200, H=136, tile_size=16, D=3, seed=32, bg=False, packed=True)
