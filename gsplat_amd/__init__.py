@@ -44,6 +44,10 @@ _LAZY = {
     "AppearanceOptModule": "appearance", "appearance": "appearance",
     # the deformation network of the dynamic-scene trainer (gsplat/contrib/dynamic/deformation.py)
     "DeformNetwork": "deformation", "DeformationTable": "deformation", "deformation": "deformation",
+    # its producer, the HexPlane feature field, and the field's regularisers (gsplat/contrib/dynamic/hexplane.py, regulation.py);
+    # `hexplane` is the module: the dispatching function is hexplane.hexplane
+    "HexPlaneField": "hexplane", "hexplane": "hexplane", "hexplane_torch": "hexplane", "plane_smoothness": "hexplane",
+    "time_smoothness": "hexplane", "time_l1": "hexplane", "hexplane_regularization": "hexplane",
     # before step 0: the nearest-neighbour scale initialisation (gsplat/init_utils.py, examples/utils.py: knn)
     "knn": "init_utils", "knn_scale_init": "init_utils", "init_utils": "init_utils",
     # on-disk formats

@@ -1080,6 +1080,36 @@ int gsx_deform_bwd(const float *plane_features, const float *W1, const float *b1
                    float *v_plane_features, float *v_W, float *v_small, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * HexPlane feature field of the dynamic-scene trainer (gsplat/contrib/dynamic/hexplane.py: HexPlaneField with grid_dimensions 2,
+ * input_coordinate_dim 4, output_coordinate_dim 32), the producer of the deformation network's plane_features. Per scale the six
+ * planes xy, xz, xt, yz, yt, zt (plane (a, b): [1, 32, res[b], res[a]], coordinate a along W) are sampled bilinearly with
+ * align_corners = true and border padding and multiplied element-wise; the scales are concatenated. x, y, z are normalised by
+ * (v - aabb[0]) * (2 / (aabb[1] - aabb[0])) - 1 with aabb [2, 3] read on the device; t is taken as it is.
+ * All float32 and contiguous. A scale has resolutions (rx, ry, rz, rt), each in [2, 2048]; res = HOST array [S][4] of them,
+ * 1 <= S <= 4. The kernels read a channel-last arena [cells][32] (16-byte aligned; a cell's 32 channels are 128 contiguous
+ * bytes) holding the planes of scale 0 in the order above, then scale 1, ...: gsx_hexplane_scale_cells cells per scale (0 for a
+ * resolution out of range).
+ *   gsx_hexplane_pack    fills one scale's part of the arena (`arena` points at it) from its six planes.
+ *   gsx_hexplane_unpack  writes every element of the six gradient tensors of a scale from its part of the gradient arena.
+ *   gsx_hexplane_fwd     xyzt [N, 4], 0 < N < 2^31; features [N, S * 32], 16-byte aligned: every element written; one launch.
+ *   gsx_hexplane_bwd     recomputes the samples. v_features [N, S * 32]. v_xyzt [N, 4]: every element written, zero along an axis
+ *                        whose index was clamped; or NULL (xyzt needs no gradient). v_arena [cells][32]: zeroed here on the stream,
+ *                        then summed with float atomic adds; or NULL (no plane needs a gradient).
+ * Every load stays inside its plane for any bit pattern of xyzt: an index is clamped to [0, size - 1] (a NaN index counts as 0)
+ * and the corner pair is (min(floor(u), size - 2), + 1). Non-finite coordinates give finite border samples and no gradient.
+ * features and v_xyzt are bit-equal between runs (the sum over a point's lanes has a fixed order); the plane gradients are
+ * float atomics and may differ in the last bits. No host read of device data. */
+int64_t gsx_hexplane_scale_cells(uint32_t rx, uint32_t ry, uint32_t rz, uint32_t rt);
+int gsx_hexplane_pack(const float *xy, const float *xz, const float *xt, const float *yz, const float *yt, const float *zt,
+                      uint32_t rx, uint32_t ry, uint32_t rz, uint32_t rt, float *arena, void *stream);
+int gsx_hexplane_unpack(const float *v_arena, uint32_t rx, uint32_t ry, uint32_t rz, uint32_t rt, float *v_xy, float *v_xz,
+                        float *v_xt, float *v_yz, float *v_yt, float *v_zt, void *stream);
+int gsx_hexplane_fwd(const float *xyzt, int64_t N, const float *aabb, const float *arena, const int32_t *res, uint32_t S,
+                     float *features, void *stream);
+int gsx_hexplane_bwd(const float *xyzt, int64_t N, const float *aabb, const float *arena, const int32_t *res, uint32_t S,
+                     const float *v_features, float *v_xyzt, float *v_arena, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact k-nearest-neighbour search of a point cloud against itself, the kernel of the scale initialisation every reference
  * trainer starts with: gsplat/init_utils.py:145 knn_scale_init (chunked torch.cdist + topk, O(N^2)) and examples/utils.py:156
  * knn (scikit-learn NearestNeighbors(n_neighbors=K).fit(x).kneighbors(x) on the host; simple_trainer.py:321).
